@@ -3,7 +3,16 @@
 com-orkut-sized RMAT graph (BASELINE.json configs[1]: DeepWalk MH sampler,
 10 walks/vertex, length 80), plus the re-walk latency of 10k-edge batches.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it builds the graph, runs W
+untimed and K timed generations and prints the result line (`value`,
+`ms_per_step`, the roofline of the timed kernel from the committed PMC
+summaries).  --dump-outputs DIR then writes a fixed, seeded sample of the
+corpus the last timed step left (DIR/walks.npy with DIR/walk_rows.npy, see
+dump_outputs).  Everything below that takes runs of its own -- the gather
+probes, the sub-records, the 8-GPU jobs, the corpus gather and the CPU
+baselines -- runs only with --full; without it those fields are null.
 
 N > 1 is launched by torch.distributed.run, one rank per GPU: every rank holds
 the replicated CSR and owns a contiguous start-vertex range of the walks
@@ -21,7 +30,7 @@ also carries `strong_scaling`: configs[1] exactly (10 walks per vertex) split N
 ways, value = its transitions / max-over-ranks time.  --scaling strong makes
 that the headline.
 
-Sub-records on rank 0 (same run): `mh_node2vec` (configs[4]'s model, p=.5
+Sub-records on rank 0 (same run, --full): `mh_node2vec` (configs[4]'s model, p=.5
 q=2 WEIGHT, on the configs[1] graph: first and warm generation, a configs[2]
 re-walk stream), `rewalk_latency_10k_batch[_deterministic]` (configs[2]),
 `streaming_rooflines` (rewalk-point scan, deterministic suffix copy, CSR move)
@@ -62,6 +71,11 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write a seeded sample of the last step's corpus to DIR/*.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline does not need: gather probes, re-walk streams, node2vec, "
+                        "per_gpu_of_8, the 8-GPU jobs, the corpus gather, strong scaling and the CPU baselines")
     p.add_argument("--scale", type=int, default=22)
     p.add_argument("--samples", type=int, default=ORKUT_EDGES)
     p.add_argument("--seed", type=int, default=2)
@@ -589,6 +603,36 @@ def timed_generation(g, steps, warmup, barrier, log_rank=None):
         kern_ms.append(g.stats()["last_walk_kernel_ms"])
     barrier()
     return time.perf_counter() - t_start, kern_ms, warm_ms
+
+
+DUMP_CHUNKS, DUMP_CHUNK_ROWS, DUMP_SEED = 128, 512, 0xD0A1
+
+
+def dump_outputs(g, out_dir, rank=0, world=1):
+    """What the last timed step left for a caller: rows of walks() (walk-major,
+    SENTINEL-padded vertex ids), as float64 so every u32 is exact.  The corpus
+    of the default workload is 13 GB, so a fixed sample is written: DUMP_CHUNKS
+    runs of DUMP_CHUNK_ROWS consecutive rows at starts drawn once from
+    DUMP_SEED (the whole corpus when it is smaller), 42 MB at L = 80.
+    DIR/walks.npy [rows][L] and DIR/walk_rows.npy [rows] (the row of walks()
+    each line is); at N > 1 each rank writes its own shard's sample with a
+    _rank<r> suffix."""
+    os.makedirs(out_dir, exist_ok=True)
+    W, Lw = g.number_of_walks, g.config.walk_length
+    if W <= DUMP_CHUNKS * DUMP_CHUNK_ROWS:
+        starts, count = np.zeros(1, dtype=np.int64), W
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        starts = np.sort(rng.choice(W // DUMP_CHUNK_ROWS, DUMP_CHUNKS, replace=False)) * DUMP_CHUNK_ROWS
+        count = DUMP_CHUNK_ROWS
+    rows = (starts[:, None] + np.arange(count, dtype=np.int64)[None, :]).reshape(-1)
+    walks = np.empty((len(rows), Lw), dtype=np.uint32)
+    for i, s in enumerate(starts):
+        g.export_walk_rows(int(s), count, walks[i * count:(i + 1) * count])
+    suffix = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(out_dir, f"walks{suffix}.npy"), walks.astype(np.float64))
+    np.save(os.path.join(out_dir, f"walk_rows{suffix}.npy"), rows.astype(np.float64))
+    log(f"[rank {rank}] wrote {len(rows)} of {W} walks to {out_dir}")
 
 
 def reduce_steps_time(torch, dist, comm_dev, steps_local, elapsed):
@@ -1162,7 +1206,9 @@ def main():
     import dynamicgraphrepresentationlearning_amd as W
 
     # the box's random-gather rate, probed on the idle GPU before anything is timed
-    live_ceiling = measure_gather_ceiling(args.gather_probes) if rank == 0 and args.gather_probes > 0 else None
+    full = args.full
+    probe = full and rank == 0 and args.gather_probes > 0
+    live_ceiling = measure_gather_ceiling(args.gather_probes) if probe else None
     if live_ceiling:
         log(f"gather_roof probes (G gathers/s): {live_ceiling}")
 
@@ -1178,8 +1224,8 @@ def main():
                         paramP=args.paramP, paramQ=args.paramQ, deterministic=args.det, seed=0x5EED)
     t0 = time.time()
     g = W.WharfMH.from_rmat(n, args.samples, 2 * n, seed=args.seed, config=cfg, device=dev)
-    # the whole CSR on the host only where the CPU baseline may need it (N = 1)
-    off, adj = g.flatten_graph() if world == 1 else (g.offsets(), None)
+    # the whole CSR on the host only where the CPU baseline may need it (N = 1, --full)
+    off, adj = g.flatten_graph() if world == 1 and full and args.cpu_baseline != "off" else (g.offsets(), None)
     deg = np.diff(off.astype(np.int64))
     shards = balanced_shards(deg, world)
     lo, hi = shards[rank]
@@ -1208,10 +1254,12 @@ def main():
     avg_kernel_ms = float(np.mean(kern_ms))
     bytes_per_step = BYTES_PER_STEP_DEEPWALK if args.model == "deepwalk" or args.det else BYTES_PER_STEP_NODE2VEC
     tag = f"gen_{args.model}_{'det' if args.det else 'mh'}_s{args.scale}"
+    if args.dump_outputs:
+        dump_outputs(g, args.dump_outputs, rank, world)
 
     # corpus reassembly for the downstream consumer: bounded full-mesh all-gatherv over RCCL (not timed in `value`)
     corpus = None
-    if dist:
+    if dist and full:
         from dynamicgraphrepresentationlearning_amd.distributed import RankFailure
         free = torch.cuda.mem_get_info(dev)[0] if comm_dev != "cpu" else (8 << 30)
         try:   # the budget is this rank's; the chunk is agreed over the ranks inside
@@ -1223,7 +1271,7 @@ def main():
 
     # strong scaling beside the weak line: configs[1] exactly (10 walks per vertex) split N ways
     strong = None
-    if world > 1 and weak:
+    if full and world > 1 and weak:
         cfg1 = W.WharfConfig(walks_per_vertex=args.wpv, walk_length=args.length, model=model,
                              paramP=args.paramP, paramQ=args.paramQ, deterministic=args.det, seed=0x5EED)
         g1 = W.WharfMH.from_rmat(n, args.samples, 2 * n, seed=args.seed, config=cfg1, device=dev)
@@ -1240,25 +1288,26 @@ def main():
     # benchmarked mode and (DeepWalk MH runs) in deterministic mode, the reference's default
     cfg2 = W.WharfConfig(walks_per_vertex=args.wpv, walk_length=args.length, model=model,
                          paramP=args.paramP, paramQ=args.paramQ, deterministic=args.det, seed=0x5EED)
-    rewalk = stream_latency(args, W, torch, cfg2, dev, world, rank, dist, comm_dev, barrier, args.rewalk_batches)
+    rewalk = stream_latency(args, W, torch, cfg2, dev, world, rank, dist, comm_dev, barrier,
+                            args.rewalk_batches if full else 0)
     rewalk_det = None
-    if args.det_rewalk_batches > 0 and not args.det and args.model == "deepwalk":
+    if full and args.det_rewalk_batches > 0 and not args.det and args.model == "deepwalk":
         cfg_det = W.WharfConfig(walks_per_vertex=args.wpv, walk_length=args.length, model=W.DEEPWALK,
                                 deterministic=True)
         rewalk_det = stream_latency(args, W, torch, cfg_det, dev, world, rank, dist, comm_dev, barrier,
                                     args.det_rewalk_batches, scan_batches=3)
     n2v = None
-    if world == 1 and args.model == "deepwalk" and not args.det and args.n2v_steps > 0:
+    if full and world == 1 and args.model == "deepwalk" and not args.det and args.n2v_steps > 0:
         n2v = node2vec_record(args, W, torch, dev, barrier, n)
 
     per8 = None
-    if world == 1 and args.per_gpu_of_8 and args.model == "deepwalk" and not args.det:
+    if full and world == 1 and args.per_gpu_of_8 and args.model == "deepwalk" and not args.det:
         torch.cuda.empty_cache()
         per8 = per_gpu_of_8(args, W, torch, dev, barrier)
 
     # BASELINE's two 8-GPU jobs on the ranks of this run (configs[3] strong, configs[4] g-of-8 weak)
     jobs = None
-    if (world > 1 or dist) and args.jobs and args.model == "deepwalk" and not args.det:
+    if full and (world > 1 or dist) and args.jobs and args.model == "deepwalk" and not args.det:
         jobs = {}
         for name in [j for j in args.jobs.split(",") if j]:
             torch.cuda.empty_cache()
@@ -1283,6 +1332,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": full,
             "ms_per_step": round(t_max / args.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": args.scaling,
@@ -1326,7 +1376,7 @@ def main():
             "dist_backend": (backend if backend == "gloo" else "nccl (RCCL)") if dist else None,
             "cpu_baseline": None,
         }
-        if world == 1 and args.cpu_baseline != "off":
+        if full and world == 1 and args.cpu_baseline != "off":
             active = int((deg > 0).sum())
             ext = cpu_baseline(args, n, active, off, adj, args.cpu_baseline)
             same = None

@@ -52,6 +52,56 @@ def test_record_bytes_per_slot(per_slot, anchors, want):
     assert bench.record_bytes_per_slot(_Handle(1 << 12, 5 << 12, per_slot), 1 << 12, anchors) == want
 
 
+class _Corpus:
+    """What dump_outputs reads: number_of_walks, config.walk_length and export_walk_rows."""
+
+    def __init__(self, walks):
+        self.rows = walks
+        self.number_of_walks = len(walks)
+        self.config = type("C", (), {"walk_length": walks.shape[1]})()
+        self.calls = 0
+
+    def export_walk_rows(self, first, count, out):
+        assert first + count <= len(self.rows) and out.flags.c_contiguous
+        out[:count] = self.rows[first:first + count]
+        self.calls += 1
+
+
+@pytest.mark.parametrize("walks", [0, 1000, bench.DUMP_CHUNKS * bench.DUMP_CHUNK_ROWS + 777])
+def test_dump_outputs_writes_a_fixed_sample_of_the_corpus(tmp_path, walks):
+    import numpy as np
+    rng = np.random.default_rng(walks)
+    corpus = rng.integers(0, 1 << 32, size=(walks, 5), dtype=np.uint64).astype(np.uint32)
+    if walks:
+        corpus[0, -1] = 0xFFFFFFFF   # a SENTINEL pad survives the float conversion exactly
+    outs = []
+    for d in ("a", "b"):
+        bench.dump_outputs(_Corpus(corpus), str(tmp_path / d))
+        outs.append((np.load(tmp_path / d / "walks.npy"), np.load(tmp_path / d / "walk_rows.npy")))
+    (w, r), (w2, r2) = outs
+    assert w.dtype == np.float64 and r.dtype == np.float64
+    assert np.array_equal(w, w2) and np.array_equal(r, r2)          # the same sample every run
+    assert len(r) == min(walks, bench.DUMP_CHUNKS * bench.DUMP_CHUNK_ROWS) and len(np.unique(r)) == len(r)
+    assert np.array_equal(w, corpus[r.astype(np.int64)].astype(np.float64))
+    # the default workload's sample (L = 80) stays under the 64 MB a dump may take
+    assert bench.DUMP_CHUNKS * bench.DUMP_CHUNK_ROWS * (80 + 1) * 8 <= 64 * 10 ** 6
+
+
+def test_dump_outputs_names_the_rank_at_more_than_one_gpu(tmp_path):
+    import numpy as np
+    bench.dump_outputs(_Corpus(np.arange(20, dtype=np.uint32).reshape(4, 5)), str(tmp_path), rank=1, world=2)
+    assert sorted(os.listdir(tmp_path)) == ["walk_rows_rank1.npy", "walks_rank1.npy"]
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+
+
 def test_cpu_cores_respects_an_explicit_request_and_the_host_share():
     info = bench.host_cpus()
     assert 1 <= info["usable"] <= info["nproc"]

@@ -6,7 +6,7 @@ these lines before the driver's 8-GPU bench (missing #1):
     bench.py's device collectives and barrier, the chunked corpus gather
     (all-gatherv and gatherv) with device buffers, and a self-peer
     batch_isend_irecv (outcome recorded, not asserted);
-  * bench.py --init-dist at N = 1 with both 8-GPU jobs shrunk by
+  * bench.py --full --init-dist at N = 1 with both 8-GPU jobs shrunk by
     --job-scale-delta -6: multi_gpu_job end to end over RCCL (generation, the
     bounded gather with its checksum of checksums, update batches, the per-rank
     all-gathers of the records).
@@ -65,7 +65,7 @@ def test_rccl_world1_collectives_and_chunked_gather(tmp_path):
 
 
 def test_bench_jobs_over_rccl_at_world1(tmp_path):
-    args = [os.path.join(REPO, "bench.py"), "--gpus", "1", "--init-dist", "--steps", "1", "--warmup", "1",
+    args = [os.path.join(REPO, "bench.py"), "--full", "--gpus", "1", "--init-dist", "--steps", "1", "--warmup", "1",
             "--scale", "16", "--samples", "400000", "--rewalk-batches", "2", "--det-rewalk-batches", "0",
             "--n2v-steps", "0", "--per-gpu-of-8", "0", "--gather-probes", "0", "--cpu-baseline", "off",
             "--job-scale-delta", "-6", "--job-batches", "2", "--gather-chunk-bytes", str(64 << 20)]

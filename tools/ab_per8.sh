@@ -11,7 +11,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 TAG=${TAG:-per8}
 REPS=${REPS:-2}
-ARGS="--steps 1 --warmup 0 --rewalk-batches 0 --det-rewalk-batches 0 --n2v-steps 0 --cpu-baseline off --gather-probes 0 ${EXTRA:-}"
+ARGS="--full --steps 1 --warmup 0 --rewalk-batches 0 --det-rewalk-batches 0 --n2v-steps 0 --cpu-baseline off --gather-probes 0 ${EXTRA:-}"
 for rep in $(seq 1 $REPS); do
     for v in "$@"; do
         name=${v%%@*}; envset=""; [ "$name" != "$v" ] && envset=${v#*@}

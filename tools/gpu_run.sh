@@ -5,7 +5,7 @@
 # Steps (each under its own time limit; the script stops at the first failure):
 #   tests[:<pytest -k expr>]  pytest -m gpu (optionally a subset)
 #   smoke                     __graft_entry__.smoke()
-#   bench[:<extra args>]      python bench.py (default line), args after ':' (use ',' for spaces)
+#   bench[:<extra args>]      python bench.py --full (the whole line), args after ':' (use ',' for spaces)
 #   rehearse                  2 gloo ranks on the one GPU: bench.py --gpus 2 at reduced scale with
 #                             BASELINE's 8-GPU jobs (configs[3], configs[4]) at scale - 4
 #   bigscale:<args>           tools/bigscale.py with args (',' for spaces)
@@ -43,12 +43,12 @@ for step in "$@"; do
         timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$log" 2>&1
         rc=$?; tail -1 "$log" ;;
     bench)
-        timeout -k 10 900 python -u bench.py $args > "$log" 2>&1
+        timeout -k 10 900 python -u bench.py --full $args > "$log" 2>&1
         rc=$?
         grep '^{' "$log" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('value', d['value'], 'frac', d['roofline']['frac'], 'ms', d['ms_per_step'])" ;;
     rehearse)
         WHARF_DIST_BACKEND=gloo OMP_NUM_THREADS=4 timeout -k 10 900 python -u -m torch.distributed.run --nnodes=1 \
-            --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 1 \
+            --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 3 --warmup 1 \
             --scale 20 --samples 29000000 --stream-samples 11000000 --rewalk-batches 5 --det-rewalk-batches 0 \
             --gather-probes 0 --job-scale-delta -4 --job-batches 3 $args > "$log" 2>&1
         rc=$? ;;
@@ -82,7 +82,7 @@ for step in "$@"; do
         unset WHARF_LIB_PATH ;;
     prof)
         timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${TAG} -o run -- \
-            python3 bench.py --steps 5 --warmup 2 --rewalk-batches 10 --det-rewalk-batches 10 --n2v-steps 0 \
+            python3 bench.py --full --steps 5 --warmup 2 --rewalk-batches 10 --det-rewalk-batches 10 --n2v-steps 0 \
             --per-gpu-of-8 0 --cpu-baseline off --gather-probes 0 > "$log" 2>&1
         rc=$? ;;
     *)

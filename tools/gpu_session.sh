@@ -20,17 +20,17 @@ for s in "$@"; do
   case $s in
     pytest) step pytest_gpu 900 python -u -m pytest tests -m gpu -q -p no:cacheprovider -rf --timeout 300 --timeout-method thread ;;
     smoke)  step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)  step bench 900 python bench.py ;;
-    prof)   step prof_bench 900 rocprofv3 --kernel-trace --stats --output-format csv -d ${OUTDIR}/prof_bench -o run -- python3 bench.py --cpu-baseline off ;;
-    pmc)    GEN="python3 bench.py --steps 2 --warmup 0 --rewalk-batches 0 --det-rewalk-batches 0 --n2v-steps 2 --n2v-rewalk-batches 0 --cpu-baseline off --per-gpu-of-8 0 --gather-probes 0"
-            STR="python3 bench.py --steps 1 --warmup 0 --rewalk-batches 0 --det-rewalk-batches 3 --n2v-steps 0 --n2v-rewalk-batches 0 --cpu-baseline off --per-gpu-of-8 0 --gather-probes 0"
+    bench)  step bench 900 python bench.py --full ;;
+    prof)   step prof_bench 900 rocprofv3 --kernel-trace --stats --output-format csv -d ${OUTDIR}/prof_bench -o run -- python3 bench.py --full --cpu-baseline off ;;
+    pmc)    GEN="python3 bench.py --full --steps 2 --warmup 0 --rewalk-batches 0 --det-rewalk-batches 0 --n2v-steps 2 --n2v-rewalk-batches 0 --cpu-baseline off --per-gpu-of-8 0 --gather-probes 0"
+            STR="python3 bench.py --full --steps 1 --warmup 0 --rewalk-batches 0 --det-rewalk-batches 3 --n2v-steps 0 --n2v-rewalk-batches 0 --cpu-baseline off --per-gpu-of-8 0 --gather-probes 0"
             step pmc_gen_fetch 600 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "k_walk" --output-format csv -d ${OUTDIR}/pmc_gen_fetch -o run -- $GEN
             step pmc_gen_write 600 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "k_walk" --output-format csv -d ${OUTDIR}/pmc_gen_write -o run -- $GEN
             step pmc_str_fetch 600 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "k_rewalk_chunked|k_rewalk_scan|k_patch_in_edges|k_patch_rev" --output-format csv -d ${OUTDIR}/pmc_str_fetch -o run -- $STR
             step pmc_str_write 600 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "k_rewalk_chunked|k_rewalk_scan|k_patch_in_edges|k_patch_rev" --output-format csv -d ${OUTDIR}/pmc_str_write -o run -- $STR
             # durations of exactly the launches the streaming PMC passes count
             step prof_str 600 rocprofv3 --kernel-trace --stats --output-format csv -d ${OUTDIR}/prof_str -o run -- $STR ;;
-    pmcstr) STR="python3 bench.py --steps 1 --warmup 0 --rewalk-batches 0 --det-rewalk-batches 3 --n2v-steps 0 --n2v-rewalk-batches 0 --cpu-baseline off --per-gpu-of-8 0 --gather-probes 0"
+    pmcstr) STR="python3 bench.py --full --steps 1 --warmup 0 --rewalk-batches 0 --det-rewalk-batches 3 --n2v-steps 0 --n2v-rewalk-batches 0 --cpu-baseline off --per-gpu-of-8 0 --gather-probes 0"
             step pmc_str_fetch 600 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "k_rewalk_chunked|k_rewalk_scan|k_patch_in_edges|k_patch_rev" --output-format csv -d ${OUTDIR}/pmc_str_fetch -o run -- $STR
             step pmc_str_write 600 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "k_rewalk_chunked|k_rewalk_scan|k_patch_in_edges|k_patch_rev" --output-format csv -d ${OUTDIR}/pmc_str_write -o run -- $STR
             step prof_str 600 rocprofv3 --kernel-trace --stats --output-format csv -d ${OUTDIR}/prof_str -o run -- $STR ;;

@@ -11,7 +11,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 log=gpurun_out/${TAG:-peak}_peak_mem.log
 timeout -k 10 900 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-    --master-port 29533 bench.py --init-dist --steps 1 --warmup 0 --rewalk-batches 0 --det-rewalk-batches 0 \
+    --master-port 29533 bench.py --full --init-dist --steps 1 --warmup 0 --rewalk-batches 0 --det-rewalk-batches 0 \
     --n2v-steps 0 --per-gpu-of-8 0 --cpu-baseline off --gather-probes 0 --jobs configs3,configs4 --job-batches 2 \
     "$@" > "$log" 2>&1
 rc=$?
