@@ -20,7 +20,8 @@ from .wharfmh import (  # noqa: F401
     szudzik64_pair,
     szudzik64_unpair,
 )
+from .sgns import SkipGram  # noqa: F401
 from ._lib import LIB_PATH  # noqa: F401
 
-__all__ = ["WharfMH", "WharfConfig", "generate_batch_of_edges", "read_adjacency_graph", "snap_to_adj",
+__all__ = ["WharfMH", "WharfConfig", "SkipGram","generate_batch_of_edges", "read_adjacency_graph", "snap_to_adj",
            "szudzik64_pair", "szudzik64_unpair", "DEEPWALK", "NODE2VEC", "RANDOM", "BURNIN", "WEIGHT", "SENTINEL"]

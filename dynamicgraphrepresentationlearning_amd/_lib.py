@@ -22,12 +22,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # WHARF_LIB_PATH: an alternative build of the same library (A/B experiments in tools/)
 LIB_PATH = os.environ.get("WHARF_LIB_PATH") or os.path.join(_HERE, "libwharf_gpu.so")
 
-ABI_VERSION = 8   # WHARF_ABI_VERSION of include/wharf_gpu.h
+ABI_VERSION = 9   # WHARF_ABI_VERSION of include/wharf_gpu.h
 WHARF_OK = 0
 WHARF_DEEPWALK, WHARF_NODE2VEC = 0, 1
 WHARF_INIT_RANDOM, WHARF_INIT_BURNIN, WHARF_INIT_WEIGHT = 0, 1, 2
 WHARF_SORTED, WHARF_REMOVE_DUPS, WHARF_APPLY_WALK_UPDATES, WHARF_AFFECTED_DEVICE = 1, 2, 4, 8
+WHARF_SGNS_SERIAL, WHARF_SGNS_WIDS_DEVICE = 1, 2
 SENTINEL = 0xFFFFFFFE
+SGNS_DROPPED = 0xFFFFFFFF   # a negative dropped because it equals the centre
 
 
 class wharf_config(C.Structure):
@@ -79,6 +81,26 @@ class wharf_memory(C.Structure):
                                           "edge_hash_bytes", "update_buffers_bytes", "scratch_bytes", "total_bytes")]
 
 
+class wharf_sgns_params(C.Structure):
+    _fields_ = [
+        ("dim", C.c_uint32),
+        ("window", C.c_uint32),
+        ("negatives", C.c_uint32),
+        ("lr", C.c_float),
+        ("pass_", C.c_uint32),   # `pass` in the header
+        ("flags", C.c_uint32),
+    ]
+
+
+class wharf_sgns_result(C.Structure):
+    _fields_ = [
+        ("loss", C.c_double),
+        ("terms", C.c_uint64),
+        ("centres", C.c_uint64),
+        ("kernel_ms", C.c_float),
+    ]
+
+
 # every symbol declared in include/wharf_gpu.h, with its ctypes signature
 _P, _U64, _U32, _I = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
 SIGNATURES = {
@@ -124,6 +146,11 @@ SIGNATURES = {
     "wharf_snap_to_adj": (_I, [C.c_char_p, C.c_char_p, _I]),
     "wharf_write_corpus": (_I, [_P, C.c_char_p, _P, _U64, _I]),
     "wharf_format_corpus": (_I, [_P, _U64, _U32, C.c_char_p, _I]),
+    "wharf_sgns_build_alias": (_I, [_P, _U64, C.c_double, _P, _P]),
+    "wharf_sgns_build_noise": (_I, [_P, C.c_double]),
+    "wharf_sgns_get_noise": (_I, [_P, _P, _P, _P]),
+    "wharf_sgns_samples": (_I, [_P, _P, _P, _U64, _P]),
+    "wharf_sgns_train": (_I, [_P, _P, _P, _P, _P, _U64, _P]),
 }
 
 

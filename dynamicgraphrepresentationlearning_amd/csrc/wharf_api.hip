@@ -147,6 +147,10 @@ struct wharf_handle {
     static constexpr uint64_t kRevMinPool = 1ull << 28;   // slots: below, the in-edge scan is as fast
     DevBuf park, parkc;                        // node2vec MH re-walk passes: two parked-walker lists, their counts
     DevBuf bdesc;                              // node2vec MH block re-walk: per 256-walk block, its run of the list
+    // skip-gram trainer (wharf_sgns.hip): vertex counts of the walk matrix and their alias table
+    // (kept until rebuilt), the listed walks' ids and columns, the call's {loss, terms, centres}
+    DevBuf sg_counts, sg_noise, sg_ids, sg_cols, sg_stat, sg_out;
+    bool sg_has_noise = false;
     uint32_t st_park_passes = 0;               // passes of the last re-walk by passes (0: lock-step kernel)
     uint64_t start_bound = 0;                  // distinct re-walk start states of the next walk update, at most (0: unknown)
     wharf_stats st{};
@@ -902,7 +906,8 @@ void free_handle(wharf_handle* h)
                       &h->bitmap, &h->counters, &h->errflag, &h->tmp, &h->k1, &h->k2, &h->flags, &h->chg, &h->cf,
                       &h->runstart, &h->runs, &h->count, &h->pairs, &h->sel, &h->defer, &h->rplan, &h->pscan,
                       &h->scratch, &h->stab, &h->preoff, &h->park, &h->parkc, &h->bdesc, &h->sanc, &h->rchunk,
-                      &h->rev, &h->srev})
+                      &h->rev, &h->srev, &h->sg_counts, &h->sg_noise, &h->sg_ids, &h->sg_cols, &h->sg_stat,
+                      &h->sg_out})
         b->release();
     h->free_snaps();
     for (auto& e : h->ev)
@@ -2251,6 +2256,165 @@ int wharf_szudzik64(int device, int op, uint64_t count, uint64_t* x, uint64_t* y
             throw;
         }
         HIPCHK(hipFree(d));
+    });
+}
+
+}  // extern "C"
+
+// ---- skip-gram training (wharf_sgns.hip) ----------------------
+
+namespace {
+
+void sgns_check_draws(const wharf_handle* h, const wharf_sgns_params* p)
+{
+    REQUIRE(p->window >= 1 && p->window <= kSgnsMaxWindow, WHARF_E_INVALID, "sgns: window must be 1..16");
+    REQUIRE(p->negatives < kSgnsMaxTargets, WHARF_E_INVALID, "sgns: negatives must be 0..15");
+    REQUIRE(p->pass < (1u << 28), WHARF_E_INVALID, "sgns: pass must be < 2^28");
+    REQUIRE(h->has_walks && h->W, WHARF_E_STATE, "sgns: the handle has no walks (WHARF_E_STATE); call wharf_generate");
+    h->check_walks();
+    REQUIRE(p->negatives == 0 || h->sg_has_noise, WHARF_E_STATE,
+            "sgns: negatives > 0 needs the noise table (WHARF_E_STATE); call wharf_sgns_build_noise");
+}
+
+// The listed walks as columns of the walk matrix in h->sg_cols (null list: column i).  Returns the
+// number of walks; an id the handle does not own raises WHARF_E_RANGE (the device has been read back).
+uint64_t sgns_columns(wharf_handle* h, const wharf_sgns_params* p, const uint32_t* wids, uint64_t count, SgnsArgs& a)
+{
+    a.walks = h->walks.as<uint32_t>();
+    a.W = h->W;
+    a.L = h->L;
+    a.sm = h->smap();
+    a.noise = h->sg_noise.as<uint2>();
+    a.n = (uint32_t)h->n;
+    a.key0 = (uint32_t)h->cfg.seed;
+    a.key1 = (uint32_t)(h->cfg.seed >> 32);
+    a.pass = p->pass;
+    a.window = p->window;
+    a.K = p->negatives;
+    a.dim = p->dim;
+    a.lr = p->lr;
+    a.cols = nullptr;
+    a.count = h->W;
+    if (!wids) return a.count;
+    a.count = count;
+    if (!count) return 0;
+    const uint32_t* dids = wids;
+    if (!(p->flags & WHARF_SGNS_WIDS_DEVICE)) {
+        h->sg_ids.ensure_grow(count * 4);
+        HIPCHK(hipMemcpyAsync(h->sg_ids.p, wids, count * 4, hipMemcpyHostToDevice, h->s));
+        dids = h->sg_ids.as<uint32_t>();
+    }
+    h->sg_cols.ensure_grow(count * 8);
+    h->sg_stat.ensure(32);
+    unsigned long long* err = h->sg_stat.as<unsigned long long>() + 3;   // the first entry not owned, or ~0
+    HIPCHK(hipMemsetAsync(err, 0xFF, 8, h->s));
+    launch_sgns_columns(dids, count, a.sm, h->wpv, h->hi, h->sg_cols.as<uint64_t>(), err, h->s);
+    unsigned long long bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, err, 8, hipMemcpyDeviceToHost, h->s));
+    h->sync();
+    REQUIRE(bad == ~0ull, WHARF_E_RANGE, "sgns: entry " + std::to_string(bad) + " of the walk id list is not owned by this handle");
+    a.cols = h->sg_cols.as<uint64_t>();
+    return count;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wharf_sgns_build_noise(wharf_handle* h, double power)
+{
+    return guarded(h, [&] {
+        REQUIRE(h, WHARF_E_INVALID, "null handle");
+        REQUIRE(power >= 0, WHARF_E_INVALID, "sgns: power must be >= 0");
+        REQUIRE(h->has_walks && h->W, WHARF_E_STATE, "sgns: the handle has no walks (WHARF_E_STATE); call wharf_generate");
+        h->check_walks();
+        h->sg_counts.ensure(h->n * 8);
+        HIPCHK(hipMemsetAsync(h->sg_counts.p, 0, h->n * 8, h->s));
+        launch_sgns_counts(h->walks.as<uint32_t>(), h->W * h->L, (uint32_t)h->n, h->sg_counts.as<unsigned long long>(), h->s);
+        HIPCHK(hipGetLastError());
+        std::vector<uint64_t> counts(h->n);
+        HIPCHK(hipMemcpyAsync(counts.data(), h->sg_counts.p, h->n * 8, hipMemcpyDeviceToHost, h->s));
+        h->sync();
+        std::vector<uint32_t> thr(h->n), alias(h->n), table(2 * h->n);
+        const int rc = wharf_sgns_build_alias(counts.data(), h->n, power, thr.data(), alias.data());
+        REQUIRE(rc == WHARF_OK, rc, "sgns: the walk matrix holds no vertex (all counts are zero)");
+        for (uint64_t v = 0; v < h->n; v++) {
+            table[2 * v] = thr[v];
+            table[2 * v + 1] = alias[v];
+        }
+        h->sg_has_noise = false;
+        h->sg_noise.ensure(h->n * 8);
+        HIPCHK(hipMemcpyAsync(h->sg_noise.p, table.data(), h->n * 8, hipMemcpyHostToDevice, h->s));
+        h->sync();
+        h->sg_has_noise = true;
+    });
+}
+
+int wharf_sgns_get_noise(wharf_handle* h, uint64_t* counts, uint32_t* thr, uint32_t* alias)
+{
+    return guarded(h, [&] {
+        REQUIRE(h, WHARF_E_INVALID, "null handle");
+        REQUIRE(h->sg_has_noise, WHARF_E_STATE, "sgns: no noise table (WHARF_E_STATE); call wharf_sgns_build_noise");
+        if (counts) HIPCHK(hipMemcpyAsync(counts, h->sg_counts.p, h->n * 8, hipMemcpyDeviceToHost, h->s));
+        std::vector<uint32_t> table(2 * h->n);
+        HIPCHK(hipMemcpyAsync(table.data(), h->sg_noise.p, h->n * 8, hipMemcpyDeviceToHost, h->s));
+        h->sync();
+        for (uint64_t v = 0; v < h->n; v++) {
+            if (thr) thr[v] = table[2 * v];
+            if (alias) alias[v] = table[2 * v + 1];
+        }
+    });
+}
+
+int wharf_sgns_samples(wharf_handle* h, const wharf_sgns_params* params, const uint32_t* wids, uint64_t count,
+                       uint32_t* out)
+{
+    return guarded(h, [&] {
+        REQUIRE(h && params && out, WHARF_E_INVALID, "null argument");
+        sgns_check_draws(h, params);
+        SgnsArgs a{};
+        const uint64_t walks = sgns_columns(h, params, wids, count, a);
+        if (!walks) return;
+        const uint64_t bytes = walks * h->L * (1 + (uint64_t)a.K) * 4;
+        h->sg_out.ensure_grow(bytes);
+        launch_sgns_samples(a, h->sg_out.as<uint32_t>(), h->s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out, h->sg_out.p, bytes, hipMemcpyDeviceToHost, h->s));
+        h->sync();
+    });
+}
+
+int wharf_sgns_train(wharf_handle* h, const wharf_sgns_params* params, float* emb_in, float* emb_out,
+                     const uint32_t* wids, uint64_t count, wharf_sgns_result* result)
+{
+    return guarded(h, [&] {
+        REQUIRE(h && params && result, WHARF_E_INVALID, "null argument");
+        REQUIRE(emb_in && emb_out, WHARF_E_INVALID, "sgns: null embedding table");
+        REQUIRE(params->dim >= 64 && params->dim <= 256 && params->dim % 64 == 0, WHARF_E_INVALID,
+                "sgns: dim must be a multiple of 64 in 64..256");
+        sgns_check_draws(h, params);
+        const bool serial = (params->flags & WHARF_SGNS_SERIAL) != 0;
+        const uint64_t listed = wids ? count : h->W;
+        REQUIRE(!serial || listed * h->L <= kSgnsSerialCap, WHARF_E_INVALID,
+                "sgns: a serial call may cover at most 2^20 walk positions");
+        SgnsArgs a{};
+        sgns_columns(h, params, wids, count, a);
+        a.emb_in = emb_in;
+        a.emb_out = emb_out;
+        h->sg_stat.ensure(32);
+        a.stat = h->sg_stat.as<unsigned long long>();
+        HIPCHK(hipMemsetAsync(h->sg_stat.p, 0, 24, h->s));
+        HIPCHK(hipEventRecord(h->ev[0], h->s));
+        launch_sgns_train(a, serial, h->s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev[1], h->s));
+        unsigned long long st[3] = {};
+        HIPCHK(hipMemcpyAsync(st, h->sg_stat.p, 24, hipMemcpyDeviceToHost, h->s));
+        h->sync();
+        std::memcpy(&result->loss, &st[0], 8);
+        result->terms = st[1];
+        result->centres = st[2];
+        result->kernel_ms = h->elapsed(0, 1);
     });
 }
 

@@ -66,6 +66,8 @@ constexpr uint32_t kFilterWords = kBloomWords + kBigBloomWords;
 
 // Philox counter word 3 = (epoch << 4) | stream
 enum : uint32_t { kStreamStep = 0, kStreamAnchor = 1, kStreamBurnin = 2, kStreamPrev = 3 };
+// skip-gram draws (wharf_sgns.hip): word 3 = (pass << 4) | stream
+enum : uint32_t { kStreamWindow = 4, kStreamNegative = 5 };
 
 // Row record: a vertex and its CSR row.  vrec[v] = {v, deg(v), off(v), epoch(v)};
 // erec[e] = vrec[adj[e]], so a walk step reads its next vertex AND that

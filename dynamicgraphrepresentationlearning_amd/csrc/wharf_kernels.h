@@ -209,4 +209,31 @@ void launch_filter_rows(const RunInfo* runs, uint64_t k, const uint32_t* pre, co
                         uint32_t* pool, hipStream_t s);
 void launch_szudzik64(int op, uint64_t cnt, uint64_t* x, uint64_t* y, uint64_t* z, hipStream_t s);
 
+// skip-gram with negative sampling over the walk matrix (wharf_sgns.hip)
+constexpr uint32_t kSgnsNone = 0xFFFFFFFFu;        // a dropped negative (equal to the centre)
+constexpr uint32_t kSgnsMaxTargets = 16;           // the centre + at most 15 negatives
+constexpr uint32_t kSgnsMaxWindow = 16;
+constexpr uint64_t kSgnsSerialCap = 1ull << 20;    // positions one serial call may cover
+struct SgnsArgs {
+    const uint32_t* walks;       // [L][W]
+    uint64_t W;
+    uint32_t L;
+    ShardMap sm;
+    const uint64_t* cols;        // the listed walks' columns, or null: column i
+    uint64_t count;
+    const uint2* noise;          // [n] alias table {thr, alias} (unused when K == 0)
+    uint32_t n;
+    uint32_t key0, key1, pass, window, K, dim;
+    float lr;
+    float* emb_in;               // [n][dim]
+    float* emb_out;              // [n][dim]
+    unsigned long long* stat;    // [0] loss (double), [1] terms, [2] centres
+};
+void launch_sgns_counts(const uint32_t* walks, uint64_t cells, uint32_t n, unsigned long long* counts, hipStream_t s);
+// wid -> column for a device id list; *err (preset to ~0) = the first entry that is not owned
+void launch_sgns_columns(const uint32_t* wids, uint64_t count, const ShardMap& sm, uint32_t wpv, uint64_t hi,
+                         uint64_t* cols, unsigned long long* err, hipStream_t s);
+void launch_sgns_samples(const SgnsArgs& a, uint32_t* out, hipStream_t s);
+void launch_sgns_train(const SgnsArgs& a, bool serial, hipStream_t s);
+
 }  // namespace wharf

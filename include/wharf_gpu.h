@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define WHARF_ABI_VERSION 8
+#define WHARF_ABI_VERSION 9
 
 enum {
     WHARF_OK = 0,
@@ -283,6 +283,58 @@ int wharf_format_corpus(const uint32_t* rows, uint64_t count, uint32_t walk_leng
  * unpair uses an exact integer square root (the reference's floor(sqrt(double))
  * is only exact below 2^52). */
 int wharf_szudzik64(int device, int op, uint64_t count, uint64_t* x, uint64_t* y, uint64_t* z);
+
+/* ---- skip-gram training on the device ----------------------- */
+
+/* The two yskip runs of vertex-classification.cpp:142-192 (a full pass over
+ * walks.txt, then --initial-model passes over the affected walks of each
+ * batch) as skip-gram with negative sampling over the resident walk matrix.
+ * Draws are Philox streams keyed by the handle's cfg.seed and `pass`. */
+enum { WHARF_SGNS_SERIAL = 1,        /* one wave runs the listed walks in list order (the reference order) */
+       WHARF_SGNS_WIDS_DEVICE = 2 }; /* wids is device memory (what WHARF_AFFECTED_DEVICE returns) */
+
+typedef struct wharf_sgns_params {
+    uint32_t dim;        /* embedding width: a multiple of 64, 64..256 */
+    uint32_t window;     /* 1..16; a centre's window is drawn from 1..window */
+    uint32_t negatives;  /* K, 0..15 */
+    float    lr;         /* learning rate */
+    uint32_t pass;       /* < 2^28; keys the draws, so two passes draw differently */
+    uint32_t flags;      /* WHARF_SGNS_* */
+} wharf_sgns_params;
+
+typedef struct wharf_sgns_result {
+    double   loss;       /* sum over the call's terms of -log sigma(+-f) */
+    uint64_t terms;      /* (context, kept target) pairs */
+    uint64_t centres;    /* walk positions trained on */
+    float    kernel_ms;  /* device time of the trainer kernel (HIP events) */
+} wharf_sgns_result;
+
+/* Host only, no handle: the alias table {thr, alias} of the weights
+ * counts[v]^power (Vose's method in double precision, deterministic order).
+ * A draw (xa, xb) yields i = (xa * n) >> 32, then xb < thr[i] ? i : alias[i].
+ * A vertex with counts[v] == 0 is never produced; all-zero counts: WHARF_E_INVALID. */
+int wharf_sgns_build_alias(const uint64_t* counts, uint64_t n, double power, uint32_t* thr, uint32_t* alias);
+
+/* Counts the vertices of the owned walk matrix on the device, builds the alias
+ * table and keeps it on the handle until the next call (re-walks do not rebuild it). */
+int wharf_sgns_build_noise(wharf_handle* h, double power);
+/* The counts and the table of the last wharf_sgns_build_noise: n entries each (any may be NULL). */
+int wharf_sgns_get_noise(wharf_handle* h, uint64_t* counts, uint32_t* thr, uint32_t* alias);
+
+/* The draws the trainer makes for the listed walks: out is host memory of
+ * count * walk_length * (1 + negatives) u32; per position {b, negatives...},
+ * b = 0 past the walk's end, 0xFFFFFFFF for a negative dropped because it equals
+ * the centre.  wids == NULL: every owned walk in ascending id (count ignored). */
+int wharf_sgns_samples(wharf_handle* h, const wharf_sgns_params* params, const uint32_t* wids, uint64_t count,
+                       uint32_t* out);
+
+/* One pass over the listed walks (wids == NULL: every owned walk).  emb_in and
+ * emb_out are device pointers on the handle's GPU to contiguous [n][dim] float32
+ * tables, updated in place.  An id the handle does not own: WHARF_E_RANGE before
+ * anything is launched.  A serial call may cover at most 2^20 walk positions
+ * (count * walk_length). */
+int wharf_sgns_train(wharf_handle* h, const wharf_sgns_params* params, float* emb_in, float* emb_out,
+                     const uint32_t* wids, uint64_t count, wharf_sgns_result* result);
 
 #ifdef __cplusplus
 }
