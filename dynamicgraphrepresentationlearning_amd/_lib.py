@@ -101,6 +101,10 @@ class wharf_sgns_result(C.Structure):
     ]
 
 
+class wharf_clf_params(C.Structure):
+    _fields_ = [("dim", C.c_uint32), ("classes", C.c_uint32)]
+
+
 # every symbol declared in include/wharf_gpu.h, with its ctypes signature
 _P, _U64, _U32, _I = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
 SIGNATURES = {
@@ -151,6 +155,9 @@ SIGNATURES = {
     "wharf_sgns_get_noise": (_I, [_P, _P, _P, _P]),
     "wharf_sgns_samples": (_I, [_P, _P, _P, _U64, _P]),
     "wharf_sgns_train": (_I, [_P, _P, _P, _P, _P, _U64, _P]),
+    "wharf_clf_minmax": (_I, [_P, _P, _U64, _U32, _P, _U64, _P, _P]),
+    "wharf_clf_loss_grad": (_I, [_P, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _P, _P]),
+    "wharf_clf_predict": (_I, [_P, _P, _P, _U64, _P, _U64, _P, _P, _P, _P, _P, _P]),
 }
 
 

@@ -151,6 +151,9 @@ struct wharf_handle {
     // (kept until rebuilt), the listed walks' ids and columns, the call's {loss, terms, centres}
     DevBuf sg_counts, sg_noise, sg_ids, sg_cols, sg_stat, sg_out;
     bool sg_has_noise = false;
+    // classifier (wharf_clf.hip): the blocks' shares of gradient and loss (min / max), the call's
+    // {loss, first bad id, first bad label}, the confusion matrix
+    DevBuf clf_partial, clf_lossp, clf_stat, clf_conf;
     uint32_t st_park_passes = 0;               // passes of the last re-walk by passes (0: lock-step kernel)
     uint64_t start_bound = 0;                  // distinct re-walk start states of the next walk update, at most (0: unknown)
     wharf_stats st{};
@@ -907,7 +910,7 @@ void free_handle(wharf_handle* h)
                       &h->runstart, &h->runs, &h->count, &h->pairs, &h->sel, &h->defer, &h->rplan, &h->pscan,
                       &h->scratch, &h->stab, &h->preoff, &h->park, &h->parkc, &h->bdesc, &h->sanc, &h->rchunk,
                       &h->rev, &h->srev, &h->sg_counts, &h->sg_noise, &h->sg_ids, &h->sg_cols, &h->sg_stat,
-                      &h->sg_out})
+                      &h->sg_out, &h->clf_partial, &h->clf_lossp, &h->clf_stat, &h->clf_conf})
         b->release();
     h->free_snaps();
     for (auto& e : h->ev)
@@ -2415,6 +2418,119 @@ int wharf_sgns_train(wharf_handle* h, const wharf_sgns_params* params, float* em
         result->terms = st[1];
         result->centres = st[2];
         result->kernel_ms = h->elapsed(0, 1);
+    });
+}
+
+}  // extern "C"
+
+// ---- vertex classification from the embeddings (wharf_clf.hip) ----
+
+namespace {
+
+void clf_check_shape(uint32_t dim, uint32_t C, uint64_t n, uint64_t count)
+{
+    REQUIRE(dim >= 64 && dim <= 256 && dim % 64 == 0, WHARF_E_INVALID, "clf: dim must be a multiple of 64 in 64..256");
+    REQUIRE(C >= 2 && C <= 256, WHARF_E_INVALID, "clf: classes must be 2..256");
+    REQUIRE(n >= 1, WHARF_E_INVALID, "clf: the table has no rows");
+    REQUIRE(count >= 1, WHARF_E_INVALID, "clf: count must be >= 1");
+}
+
+// ids < n (WHARF_E_RANGE) and labels < C (WHARF_E_INVALID), before anything else is launched
+void clf_check_lists(wharf_handle* h, const uint32_t* vids, const uint32_t* labels, uint64_t count, uint64_t n, uint32_t C)
+{
+    h->clf_stat.ensure(32);
+    unsigned long long* err = h->clf_stat.as<unsigned long long>() + 1;
+    HIPCHK(hipMemsetAsync(err, 0xFF, 16, h->s));
+    launch_clf_check(vids, labels, count, n, C, err, h->s);
+    HIPCHK(hipGetLastError());
+    unsigned long long bad[2] = {};
+    HIPCHK(hipMemcpyAsync(bad, err, 16, hipMemcpyDeviceToHost, h->s));
+    h->sync();
+    REQUIRE(bad[0] == ~0ull, WHARF_E_RANGE, "clf: entry " + std::to_string(bad[0]) + " of the id list is not below n");
+    REQUIRE(bad[1] == ~0ull, WHARF_E_INVALID,
+            "clf: entry " + std::to_string(bad[1]) + " of the label list is not below the number of classes");
+}
+
+}  // namespace
+
+extern "C" {
+
+int wharf_clf_minmax(wharf_handle* h, const float* emb, uint64_t n, uint32_t dim, const uint32_t* vids, uint64_t count,
+                     float* lo_out, float* hi_out)
+{
+    return guarded(h, [&] {
+        REQUIRE(h && emb && vids && lo_out && hi_out, WHARF_E_INVALID, "null argument");
+        clf_check_shape(dim, 2, n, count);
+        clf_check_lists(h, vids, nullptr, count, n, 2);
+        h->clf_partial.ensure_grow((size_t)clf_minmax_blocks(count, dim) * 2 * dim * 4);
+        launch_clf_minmax(emb, vids, count, dim, h->clf_partial.as<float>(), lo_out, hi_out, h->s);
+        HIPCHK(hipGetLastError());
+        h->sync();
+    });
+}
+
+int wharf_clf_loss_grad(wharf_handle* h, const wharf_clf_params* params, const float* emb, uint64_t n,
+                        const uint32_t* vids, const uint32_t* labels, uint64_t count, const float* lo,
+                        const float* scale, const float* wb, float* grad_out, double* loss_out)
+{
+    return guarded(h, [&] {
+        REQUIRE(h && params && emb && vids && labels && lo && scale && wb && grad_out && loss_out, WHARF_E_INVALID,
+                "null argument");
+        clf_check_shape(params->dim, params->classes, n, count);
+        clf_check_lists(h, vids, labels, count, n, params->classes);
+        const ClfGrid g = clf_grid(count, params->dim, params->classes);
+        h->clf_partial.ensure_grow((size_t)g.blocks * params->classes * (params->dim + 1) * 4);
+        h->clf_lossp.ensure_grow((size_t)g.blocks * 8);
+        ClfArgs a{};
+        a.emb = emb;
+        a.vids = vids;
+        a.labels = labels;
+        a.count = count;
+        a.dim = params->dim;
+        a.C = params->classes;
+        a.ct = g.ct;
+        a.lo = lo;
+        a.scale = scale;
+        a.wb = wb;
+        a.partial = h->clf_partial.as<float>();
+        a.lossp = h->clf_lossp.as<double>();
+        launch_clf_loss_grad(a, grad_out, h->clf_stat.as<double>(), h->s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(loss_out, h->clf_stat.p, 8, hipMemcpyDeviceToHost, h->s));
+        h->sync();
+    });
+}
+
+int wharf_clf_predict(wharf_handle* h, const wharf_clf_params* params, const float* emb, uint64_t n,
+                      const uint32_t* vids, uint64_t count, const float* lo, const float* scale, const float* wb,
+                      const uint32_t* labels, uint32_t* pred_out, uint64_t* confusion)
+{
+    return guarded(h, [&] {
+        REQUIRE(h && params && emb && vids && lo && scale && wb && pred_out, WHARF_E_INVALID, "null argument");
+        REQUIRE(labels || !confusion, WHARF_E_INVALID, "clf: a confusion matrix needs the labels");
+        clf_check_shape(params->dim, params->classes, n, count);
+        clf_check_lists(h, vids, labels, count, n, params->classes);
+        const size_t cbytes = (size_t)params->classes * params->classes * 8;
+        ClfArgs a{};
+        a.emb = emb;
+        a.vids = vids;
+        a.labels = labels;
+        a.count = count;
+        a.dim = params->dim;
+        a.C = a.ct = params->classes;
+        a.lo = lo;
+        a.scale = scale;
+        a.wb = wb;
+        a.pred = pred_out;
+        if (confusion) {
+            h->clf_conf.ensure(cbytes);
+            HIPCHK(hipMemsetAsync(h->clf_conf.p, 0, cbytes, h->s));
+            a.conf = h->clf_conf.as<unsigned long long>();
+        }
+        launch_clf_predict(a, h->s);
+        HIPCHK(hipGetLastError());
+        if (confusion) HIPCHK(hipMemcpyAsync(confusion, h->clf_conf.p, cbytes, hipMemcpyDeviceToHost, h->s));
+        h->sync();
     });
 }
 

@@ -236,4 +236,39 @@ void launch_sgns_columns(const uint32_t* wids, uint64_t count, const ShardMap& s
 void launch_sgns_samples(const SgnsArgs& a, uint32_t* out, hipStream_t s);
 void launch_sgns_train(const SgnsArgs& a, bool serial, hipStream_t s);
 
+// softmax-regression classifier over an embedding table (wharf_clf.hip)
+constexpr uint32_t kClfRows = 16;            // listed rows of a tile
+constexpr uint32_t kClfMaxElems = 16384;     // gradient elements a block keeps in registers (64 per thread)
+constexpr uint32_t kClfWbLds = 6144;         // wb of at most this many floats is staged in LDS by every block
+// blocks of a pass: a constant, so the grid does not depend on the device (256 CUs x 2 or 3 resident blocks divide it)
+constexpr uint32_t kClfMaxBlocks = 1536;
+struct ClfArgs {
+    const float* emb;            // [n][dim]
+    const uint32_t* vids;        // [count] rows to use
+    const uint32_t* labels;      // [count], or null (predict without a confusion matrix)
+    uint64_t count;
+    uint32_t dim, C, ct;         // ct: classes of a block's share of the gradient
+    uint32_t wlds;               // set by the launcher: wb is staged in LDS
+    const float* lo;             // [dim]
+    const float* scale;          // [dim]
+    const float* wb;             // [C][dim + 1]
+    float* partial;              // [blocks][C][dim + 1] the blocks' shares of the gradient
+    double* lossp;               // [blocks] the blocks' shares of the loss
+    uint32_t* pred;              // [count] (predict)
+    unsigned long long* conf;    // [C][C], or null (predict)
+};
+struct ClfGrid {
+    uint32_t blocks, tiles_c, ct;   // gridDim.x, gridDim.y, classes per class tile
+};
+ClfGrid clf_grid(uint64_t count, uint32_t dim, uint32_t C);   // a function of (count, dim, C) alone
+uint32_t clf_minmax_blocks(uint64_t count, uint32_t dim);
+// *err, err[1] (preset to ~0) = the first id >= n, the first label >= C (labels may be null)
+void launch_clf_check(const uint32_t* vids, const uint32_t* labels, uint64_t count, uint64_t n, uint32_t C,
+                      unsigned long long* err, hipStream_t s);
+// part: [clf_minmax_blocks][2][dim] floats
+void launch_clf_minmax(const float* emb, const uint32_t* vids, uint64_t count, uint32_t dim, float* part, float* lo,
+                       float* hi, hipStream_t s);
+void launch_clf_loss_grad(const ClfArgs& a, float* grad, double* loss, hipStream_t s);
+void launch_clf_predict(const ClfArgs& a, hipStream_t s);
+
 }  // namespace wharf

@@ -336,6 +336,43 @@ int wharf_sgns_samples(wharf_handle* h, const wharf_sgns_params* params, const u
 int wharf_sgns_train(wharf_handle* h, const wharf_sgns_params* params, float* emb_in, float* emb_out,
                      const uint32_t* wids, uint64_t count, wharf_sgns_result* result);
 
+/* ---- vertex classification from the embeddings --------------- */
+
+/* The MinMaxScaler + multinomial LogisticRegression stage of
+ * experiments/bin/vertex-classification.py over an embedding table where it
+ * lies.  Any handle will do (one from wharf_create_empty included): it gives the
+ * device, the stream and the error text.  Unless said otherwise every pointer is
+ * device memory of the handle's GPU:
+ *   emb    float32 [n][dim]          the table (e.g. SkipGram's emb_in)
+ *   vids   u32 [count]               the rows to use; repeats are allowed
+ *   lo, scale  float32 [dim]         the scaled row is x' = (x - lo) * scale
+ *   wb     float32 [classes][dim+1]  row c: the class's weights, then its bias
+ * An id >= n: WHARF_E_RANGE; a label >= classes, a bad dim / classes / count or a
+ * null pointer: WHARF_E_INVALID; both before anything is launched, outputs untouched. */
+typedef struct wharf_clf_params {
+    uint32_t dim;        /* embedding width: a multiple of 64, 64..256 */
+    uint32_t classes;    /* C, 2..256 */
+} wharf_clf_params;
+
+/* Per-column minimum and maximum over the listed rows (finite inputs), exact. */
+int wharf_clf_minmax(wharf_handle* h, const float* emb, uint64_t n, uint32_t dim, const uint32_t* vids, uint64_t count,
+                     float* lo_out, float* hi_out);
+
+/* z_ic = wb[c] . (x'_i, 1); p_i = softmax(z_i) (row maximum subtracted first);
+ * *loss_out (host) = sum_i -log p_{i,labels[i]}; grad_out (device, [classes][dim+1])
+ * = sum_i (p_ic - [labels[i] == c]) (x'_i, 1).  No regulariser.  Deterministic:
+ * the same inputs give the same bits on every call. */
+int wharf_clf_loss_grad(wharf_handle* h, const wharf_clf_params* params, const float* emb, uint64_t n,
+                        const uint32_t* vids, const uint32_t* labels, uint64_t count, const float* lo,
+                        const float* scale, const float* wb, float* grad_out, double* loss_out);
+
+/* pred_out[i] (device u32 [count]) = the lowest class that attains the maximum
+ * logit.  With labels (device, may be NULL) and confusion (host u64
+ * [classes][classes], may be NULL): confusion[t][p] = rows of true class t predicted p. */
+int wharf_clf_predict(wharf_handle* h, const wharf_clf_params* params, const float* emb, uint64_t n,
+                      const uint32_t* vids, uint64_t count, const float* lo, const float* scale, const float* wb,
+                      const uint32_t* labels, uint32_t* pred_out, uint64_t* confusion);
+
 #ifdef __cplusplus
 }
 #endif
