@@ -30,6 +30,9 @@ WHARF_SORTED, WHARF_REMOVE_DUPS, WHARF_APPLY_WALK_UPDATES, WHARF_AFFECTED_DEVICE
 WHARF_SGNS_SERIAL, WHARF_SGNS_WIDS_DEVICE = 1, 2
 SENTINEL = 0xFFFFFFFE
 SGNS_DROPPED = 0xFFFFFFFF   # a negative dropped because it equals the centre
+WHARF_EMB_DOT, WHARF_EMB_COSINE = 0, 1
+WHARF_EMB_EXCLUDE_SELF, WHARF_EMB_EXCLUDE_NEIGHBOURS = 1, 2
+EMB_NO_ID = 0xFFFFFFFF      # the id of a top-k entry past the eligible rows (its score is -inf)
 
 
 class wharf_config(C.Structure):
@@ -105,6 +108,10 @@ class wharf_clf_params(C.Structure):
     _fields_ = [("dim", C.c_uint32), ("classes", C.c_uint32)]
 
 
+class wharf_emb_params(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("dim", "metric", "k", "flags", "splits", "reserved")]
+
+
 # every symbol declared in include/wharf_gpu.h, with its ctypes signature
 _P, _U64, _U32, _I = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
 SIGNATURES = {
@@ -158,6 +165,10 @@ SIGNATURES = {
     "wharf_clf_minmax": (_I, [_P, _P, _U64, _U32, _P, _U64, _P, _P]),
     "wharf_clf_loss_grad": (_I, [_P, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _P, _P]),
     "wharf_clf_predict": (_I, [_P, _P, _P, _U64, _P, _U64, _P, _P, _P, _P, _P, _P]),
+    "wharf_emb_row_norms": (_I, [_P, _P, _U64, _U32, _P]),
+    "wharf_emb_score_pairs": (_I, [_P, _P, _P, _P, _U64, _P, _P, _P, _U64, _P]),
+    "wharf_emb_topk": (_I, [_P, _P, _P, _P, _U64, _P, _P, _P, _U64, _P, _P]),
+    "wharf_has_edges": (_I, [_P, _P, _U64, _P]),
 }
 
 

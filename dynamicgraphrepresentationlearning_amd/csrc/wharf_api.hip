@@ -154,6 +154,7 @@ struct wharf_handle {
     // classifier (wharf_clf.hip): the blocks' shares of gradient and loss (min / max), the call's
     // {loss, first bad id, first bad label}, the confusion matrix
     DevBuf clf_partial, clf_lossp, clf_stat, clf_conf;
+    DevBuf emb_cand;                           // embedding queries (wharf_emb.hip): the splits' candidates of a chunk of queries
     uint32_t st_park_passes = 0;               // passes of the last re-walk by passes (0: lock-step kernel)
     uint64_t start_bound = 0;                  // distinct re-walk start states of the next walk update, at most (0: unknown)
     wharf_stats st{};
@@ -910,7 +911,7 @@ void free_handle(wharf_handle* h)
                       &h->runstart, &h->runs, &h->count, &h->pairs, &h->sel, &h->defer, &h->rplan, &h->pscan,
                       &h->scratch, &h->stab, &h->preoff, &h->park, &h->parkc, &h->bdesc, &h->sanc, &h->rchunk,
                       &h->rev, &h->srev, &h->sg_counts, &h->sg_noise, &h->sg_ids, &h->sg_cols, &h->sg_stat,
-                      &h->sg_out, &h->clf_partial, &h->clf_lossp, &h->clf_stat, &h->clf_conf})
+                      &h->sg_out, &h->clf_partial, &h->clf_lossp, &h->clf_stat, &h->clf_conf, &h->emb_cand})
         b->release();
     h->free_snaps();
     for (auto& e : h->ev)
@@ -2530,6 +2531,136 @@ int wharf_clf_predict(wharf_handle* h, const wharf_clf_params* params, const flo
         launch_clf_predict(a, h->s);
         HIPCHK(hipGetLastError());
         if (confusion) HIPCHK(hipMemcpyAsync(confusion, h->clf_conf.p, cbytes, hipMemcpyDeviceToHost, h->s));
+        h->sync();
+    });
+}
+
+}  // extern "C"
+
+// ---- queries over the embeddings (wharf_emb.hip) ----
+
+namespace {
+
+constexpr size_t kEmbCandBytes = 64ull << 20;   // the candidates of one chunk of queries, at most
+
+void emb_check_table(uint32_t dim, uint64_t n)
+{
+    REQUIRE(dim >= 64 && dim <= 256 && dim % 64 == 0, WHARF_E_INVALID, "emb: dim must be a multiple of 64 in 64..256");
+    REQUIRE(n >= 1 && n < 0xFFFFFFFFull, WHARF_E_INVALID, "emb: n must be in 1..2^32 - 2");
+}
+
+void emb_check_params(const wharf_emb_params* p, bool topk, const float* rnorm_q, const float* rnorm_r)
+{
+    REQUIRE(p->metric == WHARF_EMB_DOT || p->metric == WHARF_EMB_COSINE, WHARF_E_INVALID, "emb: unknown metric");
+    REQUIRE(p->reserved == 0, WHARF_E_INVALID, "emb: reserved must be 0");
+    REQUIRE(p->metric != WHARF_EMB_COSINE || (rnorm_q && rnorm_r), WHARF_E_INVALID,
+            "emb: the cosine metric needs both norm buffers (wharf_emb_row_norms)");
+    if (!topk) return;
+    REQUIRE(p->k >= 1 && p->k <= kEmbMaxK, WHARF_E_INVALID, "emb: k must be 1..64");
+    REQUIRE(p->splits <= kEmbMaxSplits, WHARF_E_INVALID, "emb: splits must be 0..64");
+    REQUIRE(!(p->flags & ~(uint32_t)(WHARF_EMB_EXCLUDE_SELF | WHARF_EMB_EXCLUDE_NEIGHBOURS)), WHARF_E_INVALID,
+            "emb: unknown flag");
+}
+
+// every entry of a u32 list below n, before anything else is launched (per: entries of an item)
+void emb_check_ids(wharf_handle* h, const uint32_t* ids, uint64_t count, uint64_t n, uint32_t per, const char* what)
+{
+    h->clf_stat.ensure(32);
+    unsigned long long* err = h->clf_stat.as<unsigned long long>() + 1;
+    HIPCHK(hipMemsetAsync(err, 0xFF, 16, h->s));
+    launch_clf_check(ids, nullptr, count, n, 2, err, h->s);
+    HIPCHK(hipGetLastError());
+    unsigned long long bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, err, 8, hipMemcpyDeviceToHost, h->s));
+    h->sync();
+    REQUIRE(bad == ~0ull, WHARF_E_RANGE, std::string("emb: ") + what + " " + std::to_string(bad / per) + " has an id that is not below n");
+}
+
+}  // namespace
+
+extern "C" {
+
+int wharf_emb_row_norms(wharf_handle* h, const float* emb, uint64_t n, uint32_t dim, float* rnorm_out)
+{
+    return guarded(h, [&] {
+        REQUIRE(h && emb && rnorm_out, WHARF_E_INVALID, "null argument");
+        emb_check_table(dim, n);
+        launch_emb_row_norms(emb, n, dim, rnorm_out, h->s);
+        HIPCHK(hipGetLastError());
+        h->sync();
+    });
+}
+
+int wharf_emb_score_pairs(wharf_handle* h, const wharf_emb_params* params, const float* emb_q, const float* emb_r,
+                          uint64_t n, const float* rnorm_q, const float* rnorm_r, const uint32_t* pairs,
+                          uint64_t count, float* scores_out)
+{
+    return guarded(h, [&] {
+        REQUIRE(h && params && emb_q && emb_r && pairs && scores_out, WHARF_E_INVALID, "null argument");
+        REQUIRE(count >= 1, WHARF_E_INVALID, "emb: count must be >= 1");
+        emb_check_table(params->dim, n);
+        emb_check_params(params, false, rnorm_q, rnorm_r);
+        emb_check_ids(h, pairs, 2 * count, n, 2, "pair");
+        launch_emb_score_pairs(emb_q, emb_r, rnorm_q, rnorm_r, pairs, count, params->dim,
+                               params->metric == WHARF_EMB_COSINE, scores_out, h->s);
+        HIPCHK(hipGetLastError());
+        h->sync();
+    });
+}
+
+int wharf_emb_topk(wharf_handle* h, const wharf_emb_params* params, const float* emb_q, const float* emb_r, uint64_t n,
+                   const float* rnorm_q, const float* rnorm_r, const uint32_t* queries, uint64_t q, uint32_t* ids_out,
+                   float* scores_out)
+{
+    return guarded(h, [&] {
+        REQUIRE(h && params && emb_q && emb_r && queries && ids_out && scores_out, WHARF_E_INVALID, "null argument");
+        REQUIRE(q >= 1, WHARF_E_INVALID, "emb: q must be >= 1");
+        emb_check_table(params->dim, n);
+        emb_check_params(params, true, rnorm_q, rnorm_r);
+        const bool nb = params->flags & WHARF_EMB_EXCLUDE_NEIGHBOURS;
+        REQUIRE(!nb || (n == h->n && h->off.p && h->deg.p), WHARF_E_INVALID,
+                "emb: WHARF_EMB_EXCLUDE_NEIGHBOURS needs a table of the handle's n rows");
+        emb_check_ids(h, queries, q, n, 1, "query");
+        EmbTopkArgs a{};
+        a.emb_q = emb_q;
+        a.emb_r = emb_r;
+        a.rnorm_q = rnorm_q;
+        a.rnorm_r = rnorm_r;
+        a.n = n;
+        a.dim = params->dim;
+        a.k = params->k;
+        a.flags = params->flags;
+        a.cosine = params->metric == WHARF_EMB_COSINE;
+        a.splits = params->splits ? params->splits : emb_topk_splits(q, n);
+        if (nb) {
+            a.off = h->off.as<uint64_t>();
+            a.deg = h->deg.as<uint32_t>();
+            a.adj = h->adj.as<uint32_t>();
+        }
+        // chunks of queries, so that the candidates [splits][chunk][k] stay within kEmbCandBytes
+        const size_t per_query = (size_t)a.splits * a.k * 8;
+        const uint64_t chunk = std::max<uint64_t>(kEmbCandBytes / per_query / kEmbQueries * kEmbQueries, kEmbQueries);
+        h->emb_cand.ensure_grow((size_t)std::min<uint64_t>(chunk, q) * per_query);
+        a.cand = h->emb_cand.as<unsigned long long>();
+        for (uint64_t c0 = 0; c0 < q; c0 += chunk) {
+            a.queries = queries + c0;
+            a.q = std::min<uint64_t>(chunk, q - c0);
+            launch_emb_topk(a, ids_out + c0 * a.k, scores_out + c0 * a.k, h->s);
+            HIPCHK(hipGetLastError());
+        }
+        h->sync();
+    });
+}
+
+int wharf_has_edges(wharf_handle* h, const uint32_t* pairs, uint64_t count, uint8_t* out)
+{
+    return guarded(h, [&] {
+        REQUIRE(h && pairs && out, WHARF_E_INVALID, "null argument");
+        REQUIRE(count >= 1, WHARF_E_INVALID, "has_edges: count must be >= 1");
+        REQUIRE(h->n >= 1 && h->off.p && h->deg.p, WHARF_E_STATE, "has_edges: the handle has no graph");
+        emb_check_ids(h, pairs, 2 * count, h->n, 2, "pair");
+        launch_has_edges(h->off.as<uint64_t>(), h->deg.as<uint32_t>(), h->adj.as<uint32_t>(), pairs, count, out, h->s);
+        HIPCHK(hipGetLastError());
         h->sync();
     });
 }

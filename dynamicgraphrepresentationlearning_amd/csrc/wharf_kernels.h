@@ -271,4 +271,35 @@ void launch_clf_minmax(const float* emb, const uint32_t* vids, uint64_t count, u
 void launch_clf_loss_grad(const ClfArgs& a, float* grad, double* loss, hipStream_t s);
 void launch_clf_predict(const ClfArgs& a, hipStream_t s);
 
+// queries over an embedding table (wharf_emb.hip)
+constexpr uint32_t kEmbTile = 32;            // the MFMA tile: table rows of a slab, queries of a query tile
+// queries of a block: one tile.  Two tiles fed by one table operand (64) halve the bytes streamed, but
+// their registers and LDS leave one block a CU: 23.5 ms against 16.9 ms on the probe shape
+constexpr uint32_t kEmbQueries = 32;
+constexpr uint32_t kEmbMaxK = 64;
+constexpr uint32_t kEmbMaxSplits = 64;
+// a candidate: monotone score bits << 32 | ~id, greater = ahead; this one is {0xFFFFFFFF, -inf}, behind every row
+constexpr unsigned long long kEmbNoCand = 0x007FFFFFull << 32;
+struct EmbTopkArgs {
+    const float* emb_q;          // [n][dim]
+    const float* emb_r;          // [n][dim]
+    const float* rnorm_q;        // [n] (cosine)
+    const float* rnorm_r;        // [n] (cosine)
+    const uint32_t* queries;     // [q]
+    uint64_t q, n;
+    uint32_t dim, k, flags, splits, cosine;
+    uint32_t cap, prune_at;      // set by the launcher: a query's candidate buffer in LDS, the fill that prunes it
+    const uint64_t* off;         // the slack-row CSR (WHARF_EMB_EXCLUDE_NEIGHBOURS)
+    const uint32_t* deg;
+    const uint32_t* adj;
+    unsigned long long* cand;    // [splits][q][k] the blocks' candidates, in order
+};
+uint32_t emb_topk_splits(uint64_t q, uint64_t n);   // splits == 0: a function of (q, n) alone
+void launch_emb_row_norms(const float* emb, uint64_t n, uint32_t dim, float* rnorm, hipStream_t s);
+void launch_emb_score_pairs(const float* emb_q, const float* emb_r, const float* rnorm_q, const float* rnorm_r,
+                            const uint32_t* pairs, uint64_t count, uint32_t dim, int cosine, float* out, hipStream_t s);
+void launch_emb_topk(EmbTopkArgs a, uint32_t* ids, float* scores, hipStream_t s);
+void launch_has_edges(const uint64_t* off, const uint32_t* deg, const uint32_t* adj, const uint32_t* pairs,
+                      uint64_t count, uint8_t* out, hipStream_t s);
+
 }  // namespace wharf

@@ -222,6 +222,26 @@ class WharfMH:
         L.check(L.lib.wharf_get_graph(self._h, _ptr(off), _ptr(adj)), self._h, "flatten_graph")
         return off, adj[:m]
 
+    def has_edges(self, pairs):
+        """Node2Vec::has_edge (node2vec.h:112-119) for a list, on the current graph: pairs is
+        [count, 2] (u, v), a numpy array or an int32 / uint32 tensor on the handle's GPU; the
+        answer is a bool array or tensor of the same kind."""
+        if getattr(pairs, "is_cuda", False):
+            import torch
+            if (pairs.dtype not in (torch.int32, torch.uint32) or pairs.dim() != 2 or pairs.shape[1] != 2
+                    or not pairs.is_contiguous() or pairs.device != torch.device("cuda", self.device)):
+                raise ValueError(f"device pairs must be a contiguous 32-bit [count, 2] tensor on cuda:{self.device}")
+            out = torch.empty(pairs.shape[0], dtype=torch.uint8, device=pairs.device)
+            if pairs.shape[0]:
+                torch.cuda.synchronize(pairs.device)   # the library runs on the handle's own stream
+                L.check(L.lib.wharf_has_edges(self._h, C.c_void_p(pairs.data_ptr()), pairs.shape[0],
+                                              C.c_void_p(out.data_ptr())), self._h, "has_edges")
+            return out.bool()
+        import torch
+        host = np.ascontiguousarray(np.asarray(pairs, dtype=np.uint32).reshape(-1, 2))
+        dev = torch.from_numpy(host.view(np.int32)).to(torch.device("cuda", self.device))
+        return self.has_edges(dev).cpu().numpy()
+
     def offsets(self) -> np.ndarray:
         """CSR row offsets only (n + 1 u64; the targets stay on the device)."""
         off = np.zeros(self.number_of_vertices() + 1, dtype=np.uint64)

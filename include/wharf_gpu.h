@@ -373,6 +373,52 @@ int wharf_clf_predict(wharf_handle* h, const wharf_clf_params* params, const flo
                       const uint32_t* vids, uint64_t count, const float* lo, const float* scale, const float* wb,
                       const uint32_t* labels, uint32_t* pred_out, uint64_t* confusion);
 
+/* ---- queries over the embeddings: top-k neighbours, link scores -- */
+
+/* Exact search and pair scoring over embedding tables where they lie.  Any handle
+ * will do; WHARF_EMB_EXCLUDE_NEIGHBOURS reads the handle's current graph and needs
+ * n == the handle's n.  Every pointer is device memory of the handle's GPU:
+ *   emb_q, emb_r  float32 [n][dim]   query-side and row-side table (may be one pointer)
+ *   rnorm_q, rnorm_r  float32 [n]    wharf_emb_row_norms of the two tables (cosine only, else NULL)
+ * The dot of a pair is the k-ordered f32 chain s = fmaf(x[k], y[k], s), k = 0..dim-1,
+ * from s = 0: every entry point returns the same bits for the same pair.  Cosine is
+ * (dot * rnorm_q[u]) * rnorm_r[v].  Candidate a is ahead of b when score_a > score_b,
+ * or score_a == score_b and id_a < id_b; top-k is the first k eligible rows in that
+ * order (a zero score is reported as +0).  An id >= n: WHARF_E_RANGE; anything else
+ * wrong: WHARF_E_INVALID; both before a scoring kernel is launched, outputs untouched. */
+enum { WHARF_EMB_DOT = 0, WHARF_EMB_COSINE = 1 };
+enum { WHARF_EMB_EXCLUDE_SELF = 1, WHARF_EMB_EXCLUDE_NEIGHBOURS = 2 };
+typedef struct wharf_emb_params {
+    uint32_t dim;        /* embedding width: a multiple of 64, 64..256 */
+    uint32_t metric;     /* WHARF_EMB_DOT / WHARF_EMB_COSINE */
+    uint32_t k;          /* topk: entries per query, 1..64 (ignored by score_pairs) */
+    uint32_t flags;      /* WHARF_EMB_EXCLUDE_* (topk only) */
+    uint32_t splits;     /* topk: contiguous row ranges scanned by separate blocks and merged;
+                            0 = the library chooses; 1..64.  The result does not depend on it */
+    uint32_t reserved;   /* 0 */
+} wharf_emb_params;
+
+/* rnorm_out[v] = 1 / sqrt(dot(emb[v], emb[v])), or 0 for a row whose dot is 0. */
+int wharf_emb_row_norms(wharf_handle* h, const float* emb, uint64_t n, uint32_t dim, float* rnorm_out);
+
+/* scores_out[i] = the score of emb_q[pairs[i][0]] and emb_r[pairs[i][1]]; pairs is u32 [count][2]. */
+int wharf_emb_score_pairs(wharf_handle* h, const wharf_emb_params* params, const float* emb_q, const float* emb_r,
+                          uint64_t n, const float* rnorm_q, const float* rnorm_r, const uint32_t* pairs,
+                          uint64_t count, float* scores_out);
+
+/* For query i (row queries[i] of emb_q; repeats allowed) the k best eligible rows of
+ * emb_r: ids_out / scores_out [q][k].  Ineligible: the row whose id is the query's
+ * (EXCLUDE_SELF), the targets of the query vertex's row in the current graph
+ * (EXCLUDE_NEIGHBOURS).  Fewer than k eligible rows: the tail is {0xFFFFFFFF, -inf}. */
+int wharf_emb_topk(wharf_handle* h, const wharf_emb_params* params, const float* emb_q, const float* emb_r, uint64_t n,
+                   const float* rnorm_q, const float* rnorm_r, const uint32_t* queries, uint64_t q, uint32_t* ids_out,
+                   float* scores_out);
+
+/* Node2Vec::has_edge (node2vec.h:112-119) for a list, on the current graph:
+ * out[i] = 1 iff pairs[i][1] is in the row of pairs[i][0]; pairs is device u32
+ * [count][2], out device u8 [count].  An id >= n: WHARF_E_RANGE. */
+int wharf_has_edges(wharf_handle* h, const uint32_t* pairs, uint64_t count, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif
