@@ -112,6 +112,10 @@ class wharf_emb_params(C.Structure):
     _fields_ = [(f, C.c_uint32) for f in ("dim", "metric", "k", "flags", "splits", "reserved")]
 
 
+class wharf_kmeans_params(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("dim", "k", "flags", "reserved")]
+
+
 # every symbol declared in include/wharf_gpu.h, with its ctypes signature
 _P, _U64, _U32, _I = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
 SIGNATURES = {
@@ -169,6 +173,9 @@ SIGNATURES = {
     "wharf_emb_score_pairs": (_I, [_P, _P, _P, _P, _U64, _P, _P, _P, _U64, _P]),
     "wharf_emb_topk": (_I, [_P, _P, _P, _P, _U64, _P, _P, _P, _U64, _P, _P]),
     "wharf_has_edges": (_I, [_P, _P, _U64, _P]),
+    "wharf_kmeans_assign": (_I, [_P, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _P]),
+    "wharf_kmeans_update": (_I, [_P, _P, _P, _U64, _P, _P, _U64, _P, _P, _P]),
+    "wharf_partition_stats": (_I, [_P, _P, _U64, _U32, _P, _P]),
 }
 
 

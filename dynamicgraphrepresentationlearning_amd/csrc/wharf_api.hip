@@ -155,6 +155,9 @@ struct wharf_handle {
     // {loss, first bad id, first bad label}, the confusion matrix
     DevBuf clf_partial, clf_lossp, clf_stat, clf_conf;
     DevBuf emb_cand;                           // embedding queries (wharf_emb.hip): the splits' candidates of a chunk of queries
+    // k-means (wharf_kmeans.hip): the update's block shares (partition stats: intra | vol); hn [256],
+    // counts [256] u64, the inertia and the assign blocks' shares of it.  Not part of wharf_memory
+    DevBuf km_share, km_stat;
     uint32_t st_park_passes = 0;               // passes of the last re-walk by passes (0: lock-step kernel)
     uint64_t start_bound = 0;                  // distinct re-walk start states of the next walk update, at most (0: unknown)
     wharf_stats st{};
@@ -911,7 +914,8 @@ void free_handle(wharf_handle* h)
                       &h->runstart, &h->runs, &h->count, &h->pairs, &h->sel, &h->defer, &h->rplan, &h->pscan,
                       &h->scratch, &h->stab, &h->preoff, &h->park, &h->parkc, &h->bdesc, &h->sanc, &h->rchunk,
                       &h->rev, &h->srev, &h->sg_counts, &h->sg_noise, &h->sg_ids, &h->sg_cols, &h->sg_stat,
-                      &h->sg_out, &h->clf_partial, &h->clf_lossp, &h->clf_stat, &h->clf_conf, &h->emb_cand})
+                      &h->sg_out, &h->clf_partial, &h->clf_lossp, &h->clf_stat, &h->clf_conf, &h->emb_cand,
+                      &h->km_share, &h->km_stat})
         b->release();
     h->free_snaps();
     for (auto& e : h->ev)
@@ -2661,6 +2665,129 @@ int wharf_has_edges(wharf_handle* h, const uint32_t* pairs, uint64_t count, uint
         emb_check_ids(h, pairs, 2 * count, h->n, 2, "pair");
         launch_has_edges(h->off.as<uint64_t>(), h->deg.as<uint32_t>(), h->adj.as<uint32_t>(), pairs, count, out, h->s);
         HIPCHK(hipGetLastError());
+        h->sync();
+    });
+}
+
+}  // extern "C"
+
+// ---- k-means over the embeddings, partition statistics (wharf_kmeans.hip) ----
+
+namespace {
+
+// km_stat: hn [256] floats | counts [256] u64 | the inertia | the assign blocks' shares of it
+constexpr size_t kKmStatCounts = kKmMaxK * 4, kKmStatInertia = kKmStatCounts + kKmMaxK * 8,
+                 kKmStatParts = kKmStatInertia + 8, kKmStatBytes = kKmStatParts + (size_t)kKmMaxBlocks * 8;
+
+// the shape of a call; count becomes n when the list is null
+void km_check_shape(const wharf_kmeans_params* p, uint64_t n, const uint32_t* vids, uint64_t& count)
+{
+    REQUIRE(p->dim >= 64 && p->dim <= 256 && p->dim % 64 == 0, WHARF_E_INVALID,
+            "kmeans: dim must be a multiple of 64 in 64..256");
+    REQUIRE(p->k >= 1 && p->k <= kKmMaxK, WHARF_E_INVALID, "kmeans: k must be 1..256");
+    REQUIRE(p->flags == 0 && p->reserved == 0, WHARF_E_INVALID, "kmeans: flags and reserved must be 0");
+    REQUIRE(n >= 1 && n < 0xFFFFFFFFull, WHARF_E_INVALID, "kmeans: n must be in 1..2^32 - 2");
+    REQUIRE(!vids || count >= 1, WHARF_E_INVALID, "kmeans: count must be >= 1");
+    if (!vids) count = n;
+}
+
+// every entry of a u32 list below `limit` (and of a second list below `limit2`), before anything else is launched
+void km_check_lists(wharf_handle* h, const uint32_t* a, uint64_t limit, const char* what, const uint32_t* b,
+                    uint32_t limit2, const char* what2, uint64_t count)
+{
+    h->clf_stat.ensure(32);
+    unsigned long long* err = h->clf_stat.as<unsigned long long>() + 1;
+    HIPCHK(hipMemsetAsync(err, 0xFF, 16, h->s));
+    launch_clf_check(a, b, count, limit, limit2, err, h->s);
+    HIPCHK(hipGetLastError());
+    unsigned long long bad[2] = {};
+    HIPCHK(hipMemcpyAsync(bad, err, 16, hipMemcpyDeviceToHost, h->s));
+    h->sync();
+    REQUIRE(bad[0] == ~0ull, WHARF_E_RANGE, std::string("kmeans: entry ") + std::to_string(bad[0]) + " of the " + what + " is out of range");
+    REQUIRE(bad[1] == ~0ull, WHARF_E_RANGE, std::string("kmeans: entry ") + std::to_string(bad[1]) + " of the " + what2 + " is out of range");
+}
+
+KmArgs km_args(const wharf_kmeans_params* p, const float* emb, const float* rnorm, const uint32_t* vids, uint64_t count,
+               const float* centroids)
+{
+    KmArgs a{};
+    a.emb = emb;
+    a.rnorm = rnorm;
+    a.vids = vids;
+    a.count = count;
+    a.dim = p->dim;
+    a.k = p->k;
+    a.centroids = centroids;
+    return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wharf_kmeans_assign(wharf_handle* h, const wharf_kmeans_params* params, const float* emb, uint64_t n,
+                        const float* rnorm, const uint32_t* vids, uint64_t count, const float* centroids,
+                        uint32_t* assign_out, float* score_out, double* inertia_out)
+{
+    return guarded(h, [&] {
+        REQUIRE(h && params && emb && centroids && assign_out, WHARF_E_INVALID, "null argument");
+        km_check_shape(params, n, vids, count);
+        if (vids) km_check_lists(h, vids, n, "id list", nullptr, 2, "", count);
+        h->km_stat.ensure(kKmStatBytes);
+        char* st = h->km_stat.as<char>();
+        KmArgs a = km_args(params, emb, rnorm, vids, count, centroids);
+        a.hn = reinterpret_cast<float*>(st);
+        a.assign = assign_out;
+        a.score = score_out;
+        a.part = inertia_out ? reinterpret_cast<double*>(st + kKmStatParts) : nullptr;
+        launch_kmeans_hn(centroids, a.k, a.dim, reinterpret_cast<float*>(st), h->s);
+        launch_kmeans_assign(a, reinterpret_cast<double*>(st + kKmStatInertia), h->s);
+        HIPCHK(hipGetLastError());
+        if (inertia_out) HIPCHK(hipMemcpyAsync(inertia_out, st + kKmStatInertia, 8, hipMemcpyDeviceToHost, h->s));
+        h->sync();
+    });
+}
+
+int wharf_kmeans_update(wharf_handle* h, const wharf_kmeans_params* params, const float* emb, uint64_t n,
+                        const float* rnorm, const uint32_t* vids, uint64_t count, const uint32_t* assign,
+                        float* centroids, uint64_t* counts_out)
+{
+    return guarded(h, [&] {
+        REQUIRE(h && params && emb && assign && centroids && counts_out, WHARF_E_INVALID, "null argument");
+        km_check_shape(params, n, vids, count);
+        if (vids) km_check_lists(h, vids, n, "id list", assign, params->k, "assignment", count);
+        else km_check_lists(h, assign, params->k, "assignment", nullptr, 2, "", count);
+        const KmUpdGrid g = kmeans_update_grid(count, params->dim, params->k);
+        h->km_share.ensure((size_t)g.blocks * params->k * params->dim * 4);   // no headroom: at most 64 MB
+        h->km_stat.ensure(kKmStatBytes);
+        char* st = h->km_stat.as<char>();
+        unsigned long long* counts = reinterpret_cast<unsigned long long*>(st + kKmStatCounts);
+        HIPCHK(hipMemsetAsync(counts, 0, (size_t)params->k * 8, h->s));
+        const KmArgs a = km_args(params, emb, rnorm, vids, count, centroids);
+        launch_kmeans_update(a, assign, h->km_share.as<float>(), counts, centroids, h->s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(counts_out, counts, (size_t)params->k * 8, hipMemcpyDeviceToHost, h->s));
+        h->sync();
+    });
+}
+
+int wharf_partition_stats(wharf_handle* h, const uint32_t* part, uint64_t n, uint32_t k, uint64_t* intra_out,
+                          uint64_t* vol_out)
+{
+    return guarded(h, [&] {
+        REQUIRE(h && part && intra_out && vol_out, WHARF_E_INVALID, "null argument");
+        REQUIRE(k >= 1 && k <= 65536, WHARF_E_INVALID, "partition_stats: k must be 1..65536");
+        REQUIRE(h->n >= 1 && h->off.p && h->deg.p, WHARF_E_STATE, "partition_stats: the handle has no graph");
+        REQUIRE(n == h->n, WHARF_E_INVALID, "partition_stats: part must have the handle's n entries");
+        km_check_lists(h, part, k, "partition", nullptr, 2, "", n);
+        h->km_share.ensure((size_t)k * 16);
+        unsigned long long* intra = h->km_share.as<unsigned long long>();
+        HIPCHK(hipMemsetAsync(intra, 0, (size_t)k * 16, h->s));
+        launch_partition_stats(h->off.as<uint64_t>(), h->deg.as<uint32_t>(), h->adj.as<uint32_t>(), part, n, intra,
+                               intra + k, h->s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(intra_out, intra, (size_t)k * 8, hipMemcpyDeviceToHost, h->s));
+        HIPCHK(hipMemcpyAsync(vol_out, intra + k, (size_t)k * 8, hipMemcpyDeviceToHost, h->s));
         h->sync();
     });
 }

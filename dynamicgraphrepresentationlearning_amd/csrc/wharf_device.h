@@ -290,6 +290,48 @@ __device__ __forceinline__ void rmat_edge(const RmatParams& p, uint32_t i, uint3
 }
 
 // ---------------------------------------------------------------------------
+// embedding queries and k-means (wharf_emb.hip, wharf_kmeans.hip): the one
+// dot product, and a candidate as a 64-bit key, the score's bits made monotone in the high word
+// (a zero score as +0) and ~id in the low word, so that "ahead" is "greater key"
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long emb_key(float s, uint32_t id)
+{
+    s += 0.0f;   // -0 -> +0: float == puts them level
+    const uint32_t f = __float_as_uint(s);
+    const uint32_t u = f ^ ((f >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+    return ((unsigned long long)u << 32) | (0xFFFFFFFFu - id);
+}
+__device__ __forceinline__ float key_score(unsigned long long key)
+{
+    const uint32_t u = (uint32_t)(key >> 32);
+    return __uint_as_float((u & 0x80000000u) ? u ^ 0x80000000u : ~u);
+}
+__device__ __forceinline__ uint32_t key_id(unsigned long long key) { return 0xFFFFFFFFu - (uint32_t)key; }
+
+// orders a wave's LDS stores and loads in the compiler; the LDS itself serves one wave's accesses in issue order
+__device__ __forceinline__ void wave_lds_order()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ float chain_dot(const float* __restrict__ x, const float* __restrict__ y, uint32_t dim)
+{
+    const float4* x4 = reinterpret_cast<const float4*>(x);
+    const float4* y4 = reinterpret_cast<const float4*>(y);
+    float s = 0.f;
+    for (uint32_t c = 0; c < dim / 4; c++) {
+        const float4 a = x4[c], b = y4[c];
+        s = fmaf(a.x, b.x, s);
+        s = fmaf(a.y, b.y, s);
+        s = fmaf(a.z, b.z, s);
+        s = fmaf(a.w, b.w, s);
+    }
+    return s;
+}
+
+// ---------------------------------------------------------------------------
 // host: utility::Random (utils/utility.h:157-206).  The seed word is a signed
 // long long, so the splitmix shifts are arithmetic.
 // ---------------------------------------------------------------------------

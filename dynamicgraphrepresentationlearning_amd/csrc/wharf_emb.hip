@@ -29,20 +29,6 @@ constexpr uint32_t kBStride = kPiece + 1;   // floats of a staged row: the 32 la
 constexpr uint32_t kWaves = 4;
 constexpr unsigned long long kNoCand = kEmbNoCand;
 
-__device__ __forceinline__ unsigned long long emb_key(float s, uint32_t id)
-{
-    s += 0.0f;   // -0 -> +0: float == puts them level
-    const uint32_t f = __float_as_uint(s);
-    const uint32_t u = f ^ ((f >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-    return ((unsigned long long)u << 32) | (0xFFFFFFFFu - id);
-}
-__device__ __forceinline__ float key_score(unsigned long long key)
-{
-    const uint32_t u = (uint32_t)(key >> 32);
-    return __uint_as_float((u & 0x80000000u) ? u ^ 0x80000000u : ~u);
-}
-__device__ __forceinline__ uint32_t key_id(unsigned long long key) { return 0xFFFFFFFFu - (uint32_t)key; }
-
 // v in the ascending row adj[off, off + deg)
 __device__ __forceinline__ bool row_has(const uint32_t* __restrict__ adj, uint64_t off, uint32_t deg, uint32_t v)
 {
@@ -52,29 +38,6 @@ __device__ __forceinline__ bool row_has(const uint32_t* __restrict__ adj, uint64
         if (adj[off + mid] < v) lo = mid + 1; else hi = mid;
     }
     return lo < deg && adj[off + lo] == v;
-}
-
-// orders a wave's LDS stores and loads in the compiler; the LDS itself serves one wave's accesses in issue order
-__device__ __forceinline__ void wave_lds_order()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ float chain_dot(const float* __restrict__ x, const float* __restrict__ y, uint32_t dim)
-{
-    const float4* x4 = reinterpret_cast<const float4*>(x);
-    const float4* y4 = reinterpret_cast<const float4*>(y);
-    float s = 0.f;
-    for (uint32_t c = 0; c < dim / 4; c++) {
-        const float4 a = x4[c], b = y4[c];
-        s = fmaf(a.x, b.x, s);
-        s = fmaf(a.y, b.y, s);
-        s = fmaf(a.z, b.z, s);
-        s = fmaf(a.w, b.w, s);
-    }
-    return s;
 }
 
 __global__ __launch_bounds__(256) void k_emb_row_norms(const float* __restrict__ emb, uint64_t n, uint32_t dim,

@@ -302,4 +302,45 @@ void launch_emb_topk(EmbTopkArgs a, uint32_t* ids, float* scores, hipStream_t s)
 void launch_has_edges(const uint64_t* off, const uint32_t* deg, const uint32_t* adj, const uint32_t* pairs,
                       uint64_t count, uint8_t* out, hipStream_t s);
 
+// k-means over an embedding table, partition statistics of the graph (wharf_kmeans.hip)
+constexpr uint32_t kKmMaxK = 256;
+// listed rows of a block's group: four 32-row tiles, one per wave, fed by one staged slab of 32 centroids
+// (one tile a block: 1.29 times the time at k = 256 on the probe shape, two: 1.02)
+#ifndef WHARF_KM_WAVES
+#define WHARF_KM_WAVES 4
+#endif
+static_assert(WHARF_KM_WAVES == 1 || WHARF_KM_WAVES == 2 || WHARF_KM_WAVES == 4,
+              "k_kmeans_assign deals a slab's 16-B loads over 64, 128 or 256 threads");
+constexpr uint32_t kKmRows = 32 * WHARF_KM_WAVES;
+constexpr uint32_t kKmMaxBlocks = 16384;         // assign: blocks at most (a block takes the groups b, b + blocks, ...)
+constexpr uint32_t kKmUpdLds = 8192;             // update: floats of a block's [cluster tile][dim] sums (32 KB)
+constexpr uint32_t kKmUpdMaxBlocks = 2048;       // update: row ranges at most
+constexpr size_t kKmShareBytes = 64ull << 20;    // update: the blocks' shares [blocks][k][dim], at most
+struct KmArgs {
+    const float* emb;            // [n][dim]
+    const float* rnorm;          // [n], or null
+    const uint32_t* vids;        // [count], or null: rows 0..count-1
+    uint64_t count;
+    uint32_t dim, k;
+    const float* centroids;      // [k][dim]
+    const float* hn;             // [k] 0.5 chain(c, c)
+    uint32_t* assign;            // [count]
+    float* score;                // [count], or null
+    double* part;                // [blocks] the blocks' shares of the inertia, or null
+};
+struct KmUpdGrid {
+    uint32_t blocks, tiles_c, ct;   // gridDim.x (row ranges), gridDim.y, clusters per cluster tile
+};
+uint32_t kmeans_assign_blocks(uint64_t count);                   // a function of count alone
+KmUpdGrid kmeans_update_grid(uint64_t count, uint32_t dim, uint32_t k);   // a function of (count, dim, k) alone
+void launch_kmeans_hn(const float* centroids, uint32_t k, uint32_t dim, float* hn, hipStream_t s);
+// inertia: a device double, written when a.part is given
+void launch_kmeans_assign(const KmArgs& a, double* inertia, hipStream_t s);
+// share: [blocks][k][dim] floats; counts: [k] u64, zeroed by the caller; centroids are updated in place
+void launch_kmeans_update(const KmArgs& a, const uint32_t* assign, float* share, unsigned long long* counts,
+                          float* centroids, hipStream_t s);
+// intra, vol: [k] u64, zeroed by the caller
+void launch_partition_stats(const uint64_t* off, const uint32_t* deg, const uint32_t* adj, const uint32_t* part,
+                            uint64_t n, unsigned long long* intra, unsigned long long* vol, hipStream_t s);
+
 }  // namespace wharf

@@ -242,6 +242,25 @@ class WharfMH:
         dev = torch.from_numpy(host.view(np.int32)).to(torch.device("cuda", self.device))
         return self.has_edges(dev).cpu().numpy()
 
+    def partition_stats(self, part, k: int):
+        """A partition of the current graph's vertices: part is [n] with entries < k, a
+        numpy array or an int32 / uint32 tensor on the handle's GPU.  Returns (intra, vol), uint64 [k]
+        each: the stored slots u -> v inside cluster c, and the sum of its vertices' degrees."""
+        import torch
+        if getattr(part, "is_cuda", False):
+            if (part.dtype not in (torch.int32, torch.uint32) or not part.is_contiguous()
+                    or part.device != torch.device("cuda", self.device)):
+                raise ValueError(f"device part must be a contiguous 32-bit tensor on cuda:{self.device}")
+            dev = part.reshape(-1)
+        else:
+            host = np.ascontiguousarray(np.asarray(part), dtype=np.uint32).reshape(-1)
+            dev = torch.from_numpy(host.view(np.int32)).to(torch.device("cuda", self.device))
+        intra, vol = np.zeros(max(int(k), 1), dtype=np.uint64), np.zeros(max(int(k), 1), dtype=np.uint64)
+        torch.cuda.synchronize(dev.device)   # the library runs on the handle's own stream
+        L.check(L.lib.wharf_partition_stats(self._h, C.c_void_p(dev.data_ptr()), dev.numel(), int(k), _ptr(intra),
+                                            _ptr(vol)), self._h, "partition_stats")
+        return intra, vol
+
     def offsets(self) -> np.ndarray:
         """CSR row offsets only (n + 1 u64; the targets stay on the device)."""
         off = np.zeros(self.number_of_vertices() + 1, dtype=np.uint64)

@@ -419,6 +419,49 @@ int wharf_emb_topk(wharf_handle* h, const wharf_emb_params* params, const float*
  * [count][2], out device u8 [count].  An id >= n: WHARF_E_RANGE. */
 int wharf_has_edges(wharf_handle* h, const uint32_t* pairs, uint64_t count, uint8_t* out);
 
+/* ---- clustering from the embeddings: k-means, partition statistics -- */
+
+/* Lloyd's two passes over an embedding table where it lies.  Any handle will do.
+ * Every pointer is device memory of the handle's GPU unless said otherwise:
+ *   emb        float32 [n][dim]   the table
+ *   rnorm      float32 [n] or NULL: row i takes part as rnorm[i] * x_i (wharf_emb_row_norms:
+ *              k-means on the row-normalised table, no normalised copy)
+ *   vids       u32 [count]        the rows to cluster, repeats allowed; NULL: rows 0..n-1, count ignored
+ *   centroids  float32 [k][dim]
+ * With chain() the k-ordered f32 fmaf chain of §12 and hn[c] = 0.5f * chain(c, c), the score of
+ * row i and centroid c is s = chain(x_i, c) [* rnorm[v_i]] - hn[c] (one multiply, one subtract);
+ * the assignment is the lowest c that attains the maximum (-0 == +0), which is the nearest
+ * centroid.  Inertia = sum_i ((double)xx_i - 2 (double)s_i), xx_i = chain(x_i, x_i) [* rnorm * rnorm].
+ * The update sets centroid c to (the f32 sum of its rows, in an order fixed by (count, dim, k))
+ * / (float)count_c; a cluster without rows keeps its centroid.  No float atomics: the same
+ * inputs give the same bits on every call.  An id >= n or an assignment >= k: WHARF_E_RANGE;
+ * anything else wrong: WHARF_E_INVALID; both before a scoring kernel is launched, outputs untouched. */
+typedef struct wharf_kmeans_params {
+    uint32_t dim;        /* embedding width: a multiple of 64, 64..256 */
+    uint32_t k;          /* centroids, 1..256 */
+    uint32_t flags;      /* 0 */
+    uint32_t reserved;   /* 0 */
+} wharf_kmeans_params;
+
+/* assign_out u32 [count]; score_out float32 [count] or NULL: s(i, assign[i]); inertia_out: a host
+ * double, or NULL. */
+int wharf_kmeans_assign(wharf_handle* h, const wharf_kmeans_params* params, const float* emb, uint64_t n,
+                        const float* rnorm, const uint32_t* vids, uint64_t count, const float* centroids,
+                        uint32_t* assign_out, float* score_out, double* inertia_out);
+
+/* assign u32 [count] (device); centroids are updated in place; counts_out: host u64 [k]. */
+int wharf_kmeans_update(wharf_handle* h, const wharf_kmeans_params* params, const float* emb, uint64_t n,
+                        const float* rnorm, const uint32_t* vids, uint64_t count, const uint32_t* assign,
+                        float* centroids, uint64_t* counts_out);
+
+/* A partition of the current graph's vertices: part is device u32 [n], n the handle's n, every
+ * entry < k, k in 1..65536.  intra_out[c] = stored CSR slots (u -> v) with part[u] == part[v] == c,
+ * vol_out[c] = the sum of deg(u) over part[u] == c; both host u64 [k].  With M = sum vol,
+ * Q = sum_c (intra_c / M - (vol_c / M)^2) is Newman's modularity on a symmetric graph.
+ * A handle without a graph: WHARF_E_STATE; n other than the handle's: WHARF_E_INVALID. */
+int wharf_partition_stats(wharf_handle* h, const uint32_t* part, uint64_t n, uint32_t k, uint64_t* intra_out,
+                          uint64_t* vol_out);
+
 #ifdef __cplusplus
 }
 #endif
