@@ -24,10 +24,12 @@ from .sgns import SkipGram  # noqa: F401
 from .clf import VertexClassifier, evaluate_embeddings, lbfgs, metrics, read_labels  # noqa: F401
 from .similarity import Similarity, auc, hits_at_k, link_prediction, sample_non_edges  # noqa: F401
 from .cluster import VertexClustering, evaluate_clustering, modularity, modularity_from_stats, nmi  # noqa: F401
+from .propagate import GraphPropagation, LabelPropagation, sgc_features  # noqa: F401
 from ._lib import LIB_PATH  # noqa: F401
 
 __all__ = ["WharfMH", "WharfConfig", "SkipGram","generate_batch_of_edges", "read_adjacency_graph", "snap_to_adj",
            "szudzik64_pair", "szudzik64_unpair", "DEEPWALK", "NODE2VEC", "RANDOM", "BURNIN", "WEIGHT", "SENTINEL",
            "VertexClassifier", "evaluate_embeddings", "lbfgs", "metrics", "read_labels",
            "Similarity", "auc", "hits_at_k", "link_prediction", "sample_non_edges",
-           "VertexClustering", "evaluate_clustering", "modularity", "modularity_from_stats", "nmi"]
+           "VertexClustering", "evaluate_clustering", "modularity", "modularity_from_stats", "nmi",
+           "GraphPropagation", "LabelPropagation", "sgc_features"]

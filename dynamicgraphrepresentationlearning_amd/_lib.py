@@ -33,6 +33,8 @@ SGNS_DROPPED = 0xFFFFFFFF   # a negative dropped because it equals the centre
 WHARF_EMB_DOT, WHARF_EMB_COSINE = 0, 1
 WHARF_EMB_EXCLUDE_SELF, WHARF_EMB_EXCLUDE_NEIGHBOURS = 1, 2
 EMB_NO_ID = 0xFFFFFFFF      # the id of a top-k entry past the eligible rows (its score is -inf)
+WHARF_PROP_SELF = 1
+PROP_CHUNK = 512            # WHARF_PROP_CHUNK: the targets of a chunk partial
 
 
 class wharf_config(C.Structure):
@@ -116,6 +118,11 @@ class wharf_kmeans_params(C.Structure):
     _fields_ = [(f, C.c_uint32) for f in ("dim", "k", "flags", "reserved")]
 
 
+class wharf_prop_params(C.Structure):
+    _fields_ = [("dim", C.c_uint32), ("flags", C.c_uint32), ("alpha", C.c_float), ("beta", C.c_float),
+                ("reserved", C.c_uint32 * 2)]
+
+
 # every symbol declared in include/wharf_gpu.h, with its ctypes signature
 _P, _U64, _U32, _I = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
 SIGNATURES = {
@@ -176,6 +183,8 @@ SIGNATURES = {
     "wharf_kmeans_assign": (_I, [_P, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _P]),
     "wharf_kmeans_update": (_I, [_P, _P, _P, _U64, _P, _P, _U64, _P, _P, _P]),
     "wharf_partition_stats": (_I, [_P, _P, _U64, _U32, _P, _P]),
+    "wharf_graph_degrees": (_I, [_P, _P]),
+    "wharf_graph_propagate": (_I, [_P, _P, _P, _U64, _P, _P, _P, _P, _U64, _P]),
 }
 
 

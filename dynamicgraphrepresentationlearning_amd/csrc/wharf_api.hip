@@ -158,6 +158,8 @@ struct wharf_handle {
     // k-means (wharf_kmeans.hip): the update's block shares (partition stats: intra | vol); hn [256],
     // counts [256] u64, the inertia and the assign blocks' shares of it.  Not part of wharf_memory
     DevBuf km_share, km_stat;
+    // propagation (wharf_prop.hip): slot [n] | total, the chunk slots' vertices, the chunk partials.  Not part of wharf_memory
+    DevBuf prop_slot, prop_items, prop_part;
     uint32_t st_park_passes = 0;               // passes of the last re-walk by passes (0: lock-step kernel)
     uint64_t start_bound = 0;                  // distinct re-walk start states of the next walk update, at most (0: unknown)
     wharf_stats st{};
@@ -915,7 +917,7 @@ void free_handle(wharf_handle* h)
                       &h->scratch, &h->stab, &h->preoff, &h->park, &h->parkc, &h->bdesc, &h->sanc, &h->rchunk,
                       &h->rev, &h->srev, &h->sg_counts, &h->sg_noise, &h->sg_ids, &h->sg_cols, &h->sg_stat,
                       &h->sg_out, &h->clf_partial, &h->clf_lossp, &h->clf_stat, &h->clf_conf, &h->emb_cand,
-                      &h->km_share, &h->km_stat})
+                      &h->km_share, &h->km_stat, &h->prop_slot, &h->prop_items, &h->prop_part})
         b->release();
     h->free_snaps();
     for (auto& e : h->ev)
@@ -2788,6 +2790,89 @@ int wharf_partition_stats(wharf_handle* h, const uint32_t* part, uint64_t n, uin
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(intra_out, intra, (size_t)k * 8, hipMemcpyDeviceToHost, h->s));
         HIPCHK(hipMemcpyAsync(vol_out, intra + k, (size_t)k * 8, hipMemcpyDeviceToHost, h->s));
+        h->sync();
+    });
+}
+
+}  // extern "C"
+
+// ---- feature propagation over the graph (wharf_prop.hip) ----
+
+namespace {
+
+bool prop_overlap(const void* a, uint64_t abytes, const void* b, uint64_t bbytes)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wharf_graph_degrees(wharf_handle* h, uint32_t* deg_out_device)
+{
+    return guarded(h, [&] {
+        REQUIRE(h && deg_out_device, WHARF_E_INVALID, "null argument");
+        REQUIRE(h->n >= 1 && h->off.p && h->deg.p, WHARF_E_STATE, "graph_degrees: the handle has no graph");
+        HIPCHK(hipMemcpyAsync(deg_out_device, h->deg.p, h->n * 4, hipMemcpyDeviceToDevice, h->s));
+        h->sync();
+    });
+}
+
+int wharf_graph_propagate(wharf_handle* h, const wharf_prop_params* p, const float* x, uint64_t n, const float* wsrc,
+                          const float* wdst, const float* resid, const uint32_t* vids, uint64_t count, float* out)
+{
+    return guarded(h, [&] {
+        REQUIRE(h && p && x && out, WHARF_E_INVALID, "null argument");
+        REQUIRE(prop_dim_ok(p->dim), WHARF_E_INVALID, "propagate: dim must be 16, 32 or a multiple of 64 in 64..256");
+        REQUIRE(!(p->flags & ~(uint32_t)WHARF_PROP_SELF), WHARF_E_INVALID, "propagate: unknown flag");
+        REQUIRE(p->reserved[0] == 0 && p->reserved[1] == 0, WHARF_E_INVALID, "propagate: reserved must be 0");
+        REQUIRE(!vids || count >= 1, WHARF_E_INVALID, "propagate: count must be >= 1");
+        REQUIRE(resid || p->beta == 0.f, WHARF_E_INVALID, "propagate: beta != 0 needs resid");
+        REQUIRE(h->n >= 1 && h->off.p && h->deg.p, WHARF_E_STATE, "propagate: the handle has no graph");
+        REQUIRE(n == h->n, WHARF_E_INVALID, "propagate: x must have the handle's n rows");
+        const uint64_t rows = vids ? count : n, row_bytes = (uint64_t)p->dim * 4;
+        REQUIRE(rows < (1ull << 32), WHARF_E_INVALID, "propagate: count must be below 2^32");
+        // the kernels move rows as 16-B pieces
+        REQUIRE(!((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(resid)) & 15),
+                WHARF_E_INVALID, "propagate: x, resid and out must be 16-byte aligned");
+        REQUIRE(!prop_overlap(out, rows * row_bytes, x, n * row_bytes) &&
+                    !(resid && prop_overlap(out, rows * row_bytes, resid, n * row_bytes)),
+                WHARF_E_INVALID, "propagate: out overlaps x or resid");
+        if (vids) emb_check_ids(h, vids, count, n, 1, "entry");
+        h->prop_slot.ensure((n + 1) * 4);
+        h->prop_items.ensure_grow(prop_max_items(h->m) * 4);
+        PropArgs a{};
+        a.off = h->off.as<uint64_t>();
+        a.deg = h->deg.as<uint32_t>();
+        a.adj = h->adj.as<uint32_t>();
+        a.x = x;
+        a.wsrc = wsrc;
+        a.wdst = wdst;
+        a.resid = resid;
+        a.vids = vids;
+        a.rows = rows;
+        a.dim = p->dim;
+        a.self = p->flags & WHARF_PROP_SELF;
+        a.alpha = p->alpha;
+        a.beta = p->beta;
+        a.out = out;
+        a.slot = h->prop_slot.as<uint32_t>();
+        a.items = h->prop_items.as<uint32_t>();
+        a.total = a.slot + n;
+        HIPCHK(hipMemsetAsync(a.slot, 0xFF, n * 4, h->s));
+        HIPCHK(hipMemsetAsync(a.total, 0, 4, h->s));
+        launch_prop_rows(a, h->s);
+        HIPCHK(hipGetLastError());
+        uint32_t T = 0;
+        HIPCHK(hipMemcpyAsync(&T, a.total, 4, hipMemcpyDeviceToHost, h->s));
+        h->sync();
+        if (!T) return;
+        h->prop_part.ensure_grow((size_t)T * row_bytes);
+        a.part = h->prop_part.as<float>();
+        launch_prop_long(a, T, h->s);
+        HIPCHK(hipGetLastError());
         h->sync();
     });
 }

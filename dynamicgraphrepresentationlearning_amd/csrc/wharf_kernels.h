@@ -343,4 +343,30 @@ void launch_kmeans_update(const KmArgs& a, const uint32_t* assign, float* share,
 void launch_partition_stats(const uint64_t* off, const uint32_t* deg, const uint32_t* adj, const uint32_t* part,
                             uint64_t n, unsigned long long* intra, unsigned long long* vol, hipStream_t s);
 
+// feature propagation over the graph (wharf_prop.hip)
+struct PropArgs {
+    const uint64_t* off;         // the slack-row CSR: row v is adj[off[v], off[v] + deg[v]), ascending
+    const uint32_t* deg;
+    const uint32_t* adj;
+    const float* x;              // [n][dim]
+    const float* wsrc;           // [n], or null
+    const float* wdst;           // [n], or null
+    const float* resid;          // [n][dim], or null
+    const uint32_t* vids;        // [rows], or null: rows 0..rows-1
+    uint64_t rows;
+    uint32_t dim, self;
+    float alpha, beta;
+    float* out;                  // [rows][dim]
+    uint32_t* slot;              // [n] all ones on entry; the first chunk slot of a vertex with a long row
+    uint32_t* items;             // [prop_max_items(m)] the vertex of every reserved chunk slot
+    uint32_t* total;             // zero on entry; the chunk slots reserved
+    float* part;                 // [total][dim] the chunk partials (launch_prop_long)
+};
+bool prop_dim_ok(uint32_t dim);
+uint64_t prop_max_items(uint64_t m);   // chunk slots at most, m the stored targets of the graph
+// every row of at most WHARF_PROP_CHUNK targets, and the reservation of the others' chunk slots
+void launch_prop_rows(const PropArgs& a, hipStream_t s);
+// the other rows: T = *total chunk partials, then their sums in chunk order
+void launch_prop_long(const PropArgs& a, uint32_t T, hipStream_t s);
+
 }  // namespace wharf

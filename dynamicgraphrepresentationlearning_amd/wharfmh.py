@@ -261,6 +261,20 @@ class WharfMH:
                                             _ptr(vol)), self._h, "partition_stats")
         return intra, vol
 
+    def degrees(self, out=None):
+        """The current degrees (the out-degrees of a directed graph): an int32 tensor [n] on the handle's
+        GPU, copied device to device.  out: a contiguous int32 / uint32 [n] tensor there."""
+        import torch
+        n, dev = self.number_of_vertices(), torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty(n, dtype=torch.int32, device=dev)
+        elif (out.dtype not in (torch.int32, torch.uint32) or out.numel() != n or not out.is_contiguous()
+                or out.device != dev):
+            raise ValueError(f"out must be a contiguous 32-bit [{n}] tensor on {dev}")
+        torch.cuda.synchronize(dev)   # the library runs on the handle's own stream
+        L.check(L.lib.wharf_graph_degrees(self._h, C.c_void_p(out.data_ptr())), self._h, "graph_degrees")
+        return out
+
     def offsets(self) -> np.ndarray:
         """CSR row offsets only (n + 1 u64; the targets stay on the device)."""
         off = np.zeros(self.number_of_vertices() + 1, dtype=np.uint64)

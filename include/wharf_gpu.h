@@ -462,6 +462,47 @@ int wharf_kmeans_update(wharf_handle* h, const wharf_kmeans_params* params, cons
 int wharf_partition_stats(wharf_handle* h, const uint32_t* part, uint64_t n, uint32_t k, uint64_t* intra_out,
                           uint64_t* vol_out);
 
+/* ---- feature propagation over the current graph: Y = alpha D_l (A + s I) D_r X + beta R -- */
+
+#define WHARF_PROP_CHUNK 512u   /* targets of a chunk partial: part of the numeric contract below */
+#define WHARF_PROP_SELF  1u     /* add the vertex's own row as a last term (s = 1) */
+
+/* Every pointer of wharf_graph_propagate is device memory of the handle's GPU; the rows are the
+ * handle's current rows (the out-neighbours on a directed graph), targets ascending.
+ *   x      float32 [n][dim], n the handle's n
+ *   wsrc   float32 [n] or NULL   the weight of a source row u (D_r)
+ *   wdst   float32 [n] or NULL   the weight of the destination v (D_l)
+ *   resid  float32 [n][dim] or NULL (then beta must be 0)
+ *   vids   u32 [count] or NULL: every vertex, count ignored; repeats allowed, any order
+ *   out    float32 [count or n][dim]; its bytes overlap neither x's nor resid's
+ * Output row i, v = vids[i] (or i), column k, the row's targets u_0 < u_1 < ... < u_{d-1}, every
+ * operation a single float32 round-to-nearest multiply or add, none fused:
+ *   t_e = wsrc[u_e] * x[u_e][k]                       (x[u_e][k] itself without wsrc)
+ *   P_c = ((+0 + t_{512 c}) + t_{512 c + 1}) + ...    over the chunk's at most WHARF_PROP_CHUNK targets
+ *   A   = (P_0 + P_1) + P_2 ...                       (+0 when d = 0)
+ *   A   = A + t_v                                     with WHARF_PROP_SELF
+ *   y   = wdst[v] * A                                 (A itself without wdst)
+ *   out[i][k] = alpha * y + beta * resid[v][k]        (alpha * y without resid)
+ * No float atomics: the bits depend on the inputs alone, not on the grid, on vids or on the path
+ * a row took.  An id >= n: WHARF_E_RANGE; a handle without a graph: WHARF_E_STATE; anything else
+ * wrong (dim, flags, reserved, a null params / x / out, vids with count 0 or count >= 2^32, n other
+ * than the handle's, beta != 0 without resid, an overlap): WHARF_E_INVALID.  All before a kernel
+ * is launched, out untouched. */
+typedef struct wharf_prop_params {
+    uint32_t dim;           /* 16, 32, or a multiple of 64 in 64..256 */
+    uint32_t flags;         /* WHARF_PROP_SELF or 0 */
+    float    alpha, beta;
+    uint32_t reserved[2];   /* 0 */
+} wharf_prop_params;
+
+/* The current degrees (the row lengths wharf_graph_propagate walks): deg_out_device is device
+ * u32 [n] on the handle's GPU.  A handle without a graph: WHARF_E_STATE. */
+int wharf_graph_degrees(wharf_handle* h, uint32_t* deg_out_device);
+
+int wharf_graph_propagate(wharf_handle* h, const wharf_prop_params* p, const float* x, uint64_t n,
+                          const float* wsrc, const float* wdst, const float* resid, const uint32_t* vids,
+                          uint64_t count, float* out);
+
 #ifdef __cplusplus
 }
 #endif
